@@ -1,7 +1,14 @@
 """Benchmark: BASELINE.json metric on config C4 (10k-rule WAF signature set over URI / args /
 headers / <= 8 KB body), 10M requests per GPU, requests resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--requests R] [--pool P] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--requests R] [--pool P]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-alone] [--stress-requests S]]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline and the
+figures read off those same steps (stage times, the scan's roofline fraction, the committed
+same-tree profile).  --full adds the legs that take runs of their own: the scan alone, the C4
+stress variant and the CPU baseline (each can be switched off: --no-alone, --stress-requests 0,
+--no-cpu).  --dump-outputs DIR writes what the last timed step returned (dump_outputs below).
 
 N > 1 is launched by torch.distributed.run (one rank per GPU); requests shard with no data-path
 collective (weak scaling: every rank classifies its own R requests); the per-location and
@@ -53,12 +60,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--requests", type=int, default=10_000_000)
     ap.add_argument("--pool", type=int, default=1_000_000)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline: the scan alone, the C4 "
+                         "stress variant and the CPU baseline (keys roofline.scan_alone_ms / frac_alone, "
+                         "stage_ms.route_alone, stress, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64): the verdicts of a "
+                         "fixed seeded sample of the requests, and the hit ids")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: wall time of the CPU baseline's sample")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--stress-requests", type=int, default=2_000_000,
-                    help="the C4 stress variant's batch (0: skip); reported under the line's 'stress' key")
+                    help="--full: the C4 stress variant's batch (0: skip); reported under the line's 'stress' key")
     ap.add_argument("--no-alone", action="store_true",
-                    help="skip the scan-alone measurement (profiling runs: kernel stats of the pipeline only)")
+                    help="--full without the scan-alone measurement")
     ap.add_argument("--serial", action="store_true",
                     help="measurement: the route stage alone before the scan (GM_CREATE_SERIAL)")
     ap.add_argument("--config", default="c4", choices=("c4", "c5"),
@@ -74,6 +88,8 @@ def main():
                     help="measure a library built with measurement / tuning macros (gm_stats build_flags != 0); "
                          "the line is then marked \"build\": \"nondefault\" and is not a headline number")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "c5":
         return c5_main(args)
 
@@ -233,7 +249,10 @@ def main():
     result["roofline"].update(profiled(zone_bytes, st["csrc_hash"]))
     if st["build_flags"]:
         result["build"] = f"nondefault (build_flags {st['build_flags']:#x})"
-    if world == 1 and not args.serial and not args.no_alone:
+    if args.dump_outputs:   # the last timed step ran on stream (steps - 1) % D
+        j = (args.steps - 1) % D
+        dump_outputs(torch, args.dump_outputs, outs[j], n, hitss[j], int(s["last_hits"]))
+    if args.full and world == 1 and not args.serial and not args.no_alone:
         # the scan kernel alone (GM_CREATE_SERIAL: the route first, then the scan on its own), on
         # the same resident batch: its own roofline fraction beside the in-pipeline one above,
         # where the route shares the CUs
@@ -252,11 +271,11 @@ def main():
         result["roofline"]["scan_alone_ms"] = a_ms
         result["stage_ms"]["route_alone"] = float(np.mean(alone_route))
         result["roofline"]["frac_alone"] = zone_bytes / (a_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS
-    if world == 1 and args.stress_requests > 0:
+    if args.full and world == 1 and args.stress_requests > 0:
         del d_arena, d_reqs, d_out, d_hits
         torch.cuda.empty_cache()
         result["stress"] = stress_leg(torch, engine, records, workloads, args, local)
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(ss, gblob, preqs, parena, args.cpu_seconds)
     if dist:
         dist.destroy_process_group()
@@ -341,6 +360,8 @@ def c5_main(args):
     routed = int(tot[:st["n_locations"]].sum())
     log(f"[rank {rank}] {args.steps} steps in {elapsed:.3f}s; job-wide location hits {routed}")
     if rank == 0:
+        if args.dump_outputs:   # every batch wrote its slice of d_out; the hit ids are per batch and not kept
+            dump_outputs(torch, args.dump_outputs, d_out, n)
         print(json.dumps({
             "metric": "requests/sec (C5: mergeable Ingresses, 1k hosts incl. wildcard TLS, request stream sharded "
                       "over the GPUs, hit-counter all-reduce)",
@@ -356,6 +377,45 @@ def c5_main(args):
             "job_location_hits": routed}), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 0xC0FFEE + 7     # the sampled request positions (numpy PCG64)
+DUMP_MAX_VERDICTS = 250_000  # x 12 fields x 8 bytes = 24 MB
+DUMP_MAX_HITS = 2_000_000    # x 8 bytes = 16 MB
+
+
+def dump_outputs(torch, out_dir, d_out, n, d_hits=None, n_hits=0):
+    """--dump-outputs: what the caller of the last timed step received, as float64 .npy files (every
+    field is an integer below 2^53, so the values are exact), 40 MB at the most:
+
+      verdicts.npy  [m, 12]  the gm_verdict fields (records.VERDICT_DTYPE order) of m = min(n, 250k)
+                             requests: all of them, or a sorted sample drawn with a fixed seed
+      hits.npy      [h]      the batch's hit ids in the order the library wrote them: all of them up
+                             to 2M, beyond that a sorted sample drawn with the same seed
+      counts.npy    [2]      n and the batch's number of hit ids
+
+    The workload is generated from fixed seeds, so two builds of the library run with the same
+    arguments write files that can be compared value for value."""
+    from gpumatch.records import VERDICT_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(total, cap):
+        if total <= cap:
+            return None
+        return torch.from_numpy(np.sort(rng.choice(total, size=cap, replace=False))).to(d_out.device)
+
+    rows = d_out[:n * 32].view(n, 32)
+    idx = sample(n, DUMP_MAX_VERDICTS)
+    v = (rows if idx is None else rows[idx]).cpu().numpy().reshape(-1).view(VERDICT_DTYPE)
+    np.save(os.path.join(out_dir, "verdicts.npy"),
+            np.stack([v[f].astype(np.float64) for f in VERDICT_DTYPE.names], axis=1))
+    if d_hits is not None:
+        idx = sample(n_hits, DUMP_MAX_HITS)
+        h = (d_hits[:n_hits] if idx is None else d_hits[idx]).cpu().numpy().view(np.uint32)
+        np.save(os.path.join(out_dir, "hits.npy"), h.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([n, n_hits], dtype=np.float64))
+    log(f"outputs of the last timed step written to {out_dir}")
 
 
 def stress_leg(torch, engine, records, workloads, args, local):

@@ -9,6 +9,7 @@ if [ -n "$PYTEST_K" ]; then
   timeout -k 10 600 python -u -m pytest tests -x -q -m gpu -k "$PYTEST_K" --timeout 300 --timeout-method thread -p no:cacheprovider > gpurun_out/ab_tests_${TAG}.log 2>&1
   rc=$?; tail -3 gpurun_out/ab_tests_${TAG}.log; [ $rc -eq 0 ] || exit $rc
 fi
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the scan-alone leg (route_alone, frac_alone) is read below
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in "$@"; do
     if [ "$v" = main ]; then lib=""; else lib="$GRAFT_REPO_ROOT/exp/$v/libgpumatch.so"; fi

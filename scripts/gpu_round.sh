@@ -12,6 +12,7 @@ if [ -z "$NO_TESTS" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ -z "$NO_BENCH" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS}"   # the whole line: scan alone, stress leg, CPU baseline
   timeout -k 10 400 python -u bench.py ${BENCH_ARGS} > gpurun_out/bench_${TAG}.log 2>&1
   rc=$?
   tail -4 gpurun_out/bench_${TAG}.log

@@ -3,6 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 TAG=${TAG:-r6}
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the stress leg's line is read below
 timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread -p no:cacheprovider > gpurun_out/gpu_tests_${TAG}.log 2>&1
 rc=$?; echo "pytest exit=$rc" >> gpurun_out/gpu_tests_${TAG}.log; tail -4 gpurun_out/gpu_tests_${TAG}.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 400 python -u bench.py --no-cpu ${BENCH_ARGS} > gpurun_out/bench_${TAG}.log 2>&1
