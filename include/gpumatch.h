@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 10u  /* 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
+#define GM_ABI_VERSION 11u  /* 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
                                7: GM_ACT_TOO_LARGE, GM_REQ_CHUNKED, gm_rejects, build flags; 6: n_rsl_reversed;
                                5: gm_update_upstream / gm_peers_migrate; 4: union-DFA stats */
 
@@ -258,7 +258,8 @@ typedef struct gm_stats_t {
     /* of n_rsl_slices: anchored and reversed slices run only over the requests their head map
      * admits (the first, or for a reversed slice the last, three $uri bytes) */
     uint32_t n_rsl_heads;
-    uint32_t reserved0;
+    /* gzip bodies given an inflated view in the last batch (GM_DEC_GZIP) */
+    uint32_t last_inflated;
     /* the source hash the library was built from (scripts/scan_profile.py csrc_hash: sha256 over
      * the files of ingress-plus_amd/csrc and include/gpumatch.h, first 16 hex digits as a number; 0 = unknown):
      * a profile or bench line names the build it measured, not the tree beside it */
@@ -277,11 +278,15 @@ typedef struct gm_stats_t {
  *   percent   %XX -> byte in $args (and a form body)
  *   urlenc    '+' -> ' ' in $args and an application/x-www-form-urlencoded body
  *   json_doc  JSON string escapes (\" \\ \/ \b \f \n \r \t \uXXXX -> UTF-8) of a "json" body
- *   base64    every run of >= 16 base64 characters in $args / the body, decoded */
+ *   base64    every run of >= 16 base64 characters in $args / the body, decoded
+ *   gzip      a body that is a gzip member (1f 8b 08 ..., whatever Content-Encoding says), inflated
+ *             (gm_inflate_bodies below); the view, its form / JSON transform by the body's
+ *             Content-Type and its base64 runs are scanned after the raw body's parts */
 #define GM_DEC_PERCENT 0x1u
 #define GM_DEC_URLENC  0x2u
 #define GM_DEC_JSON    0x4u
 #define GM_DEC_BASE64  0x8u
+#define GM_DEC_GZIP    0x10u
 
 typedef struct gm_ctx gm_ctx;
 
@@ -423,6 +428,20 @@ int         gm_parse_requests(gm_ctx *ctx, const uint8_t *wire, const gm_wire_ms
  * 3 * uri_len + args_len + ruri_len + 1) always suffices.  Device pointers, asynchronous. */
 int         gm_upstream_uris(gm_ctx *ctx, const gm_batch *in, const gm_verdict *verdicts, uint8_t *out,
                              uint64_t out_cap, uint64_t *out_off, uint32_t *out_len, void *stream);
+
+/* ---------------------------------------------------------------- gzip request bodies
+ * (Wallarm's `gzip` parser.)  The first RFC 1952 member of every body that is one
+ * (it starts 1f 8b 08, reserved FLG bits zero, >= 18 bytes), inflated on the device, a wave per
+ * stream.  Request i's slot is L = min(ISIZE, GM_INFLATE_RATIO (8) * body_len, GM_INFLATE_MAX
+ * (1 MiB)) bytes: a longer stream is cut at L.  CRC-32 is not verified; a malformed stream, or one
+ * whose size differs from ISIZE, is corrupt.
+ * out_len[i] = inflated length of request i's body at out[out_off[i]] (cut at the documented limit),
+ * GM_NONE: not a gzip member, or corrupt (or past out_cap: gm_sync then reports GM_E_OVERFLOW).
+ * out_cap >= GM_INFLATE_RATIO * in->arena_len always suffices.  Device pointers, asynchronous on
+ * `stream`, completed by gm_sync.  Needs no generation: the kernel gm_match_batch runs for a
+ * signature set that declares `gzip`. */
+int         gm_inflate_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
+                              uint64_t *out_off, uint32_t *out_len, void *stream);
 
 /* ---------------------------------------------------------------- upstream peer selection
  * (the step after the path.)  The upstream blocks the templates render

@@ -32,6 +32,9 @@ int gm_debug_server(struct gm_ctx *ctx, uint32_t sid, uint32_t *out, size_t cap)
  * classes); returns the u32 count. */
 int gm_debug_alw_slices(struct gm_ctx *ctx, uint32_t *out, size_t cap);
 int gm_debug_waf_keys(struct gm_ctx *ctx, uint32_t *out, size_t cap);
+/* The request parsers (GM_DEC_* bits) location `loc` of the live generation runs: the signature
+ * set's "@decoders" minus wallarm_parser_disable; < 0: no such location. */
+int gm_debug_loc_decoders(struct gm_ctx *ctx, uint32_t loc);
 /* The prefilter's literal table: one row of 4 x uint32 per (key window, pattern) entry --
  * {key, rule id or regex index, (uint16)key_off | len << 16, flags | zones << 8}; returns the
  * number of entries (writes at most `cap` rows). */

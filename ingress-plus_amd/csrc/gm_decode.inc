@@ -18,6 +18,9 @@
 //             U+FFFD) -> UTF-8; any other backslash pair stays as is
 //   base64: a maximal run of >= 16 characters of [A-Za-z0-9+/]; its first 4 * floor(len / 4)
 //           characters decoded (padding and a partial quantum ignored)
+//   gzip: a body that is a gzip member, inflated to P (gm_inflate.inc, run before these passes);
+//         after the body's parts above: [P] [the form / JSON transform of P by the body's kind, if
+//         it changes a byte] [each base64 run of P, decoded]
 // One lane per request (byte loops over $args and the body); two passes around an exclusive scan.
 
 constexpr uint32_t B64_MIN_RUN = 16;
@@ -161,8 +164,31 @@ __device__ uint32_t body_kind(const uint8_t *A, const Rec &r, uint64_t hdrs) {
     return 0;
 }
 
-// shadow record of request i: sizes (d = nullptr) or bytes at d; returns {args', body'} lengths
-__device__ uint2 dec_one(const uint8_t *A, const Rec &r, uint32_t mask, uint8_t *d) {
+// the body's transform by its kind, then its base64 runs, of s[0, n) -> db + b (nullptr: sizes)
+__device__ uint32_t dec_body(const uint8_t *s, uint32_t n, uint32_t kind, uint32_t mask, uint8_t *db, uint32_t b) {
+    if (kind == 1 && (mask & (DEC_PERCENT | DEC_URLENC))) {
+        bool chg = false;
+        const uint32_t k = dec_form(s, n, mask, nullptr, chg);
+        if (chg) {
+            if (db) { dec_form(s, n, mask, db + b, chg); db[b + k] = '\n'; }
+            b += k + 1;
+        }
+    } else if (kind == 2 && (mask & DEC_JSON)) {
+        bool chg = false;
+        const uint32_t k = dec_json(s, n, nullptr, chg);
+        if (chg) {
+            if (db) { dec_json(s, n, db + b, chg); db[b + k] = '\n'; }
+            b += k + 1;
+        }
+    }
+    if (mask & DEC_BASE64) b += dec_b64(s, n, db ? db + b : nullptr);
+    return b;
+}
+
+// shadow record of request i: sizes (d = nullptr) or bytes at d; returns {args', body'} lengths.
+// P[0, pn): the body inflated (pn = GM_NONE: none)
+__device__ uint2 dec_one(const uint8_t *A, const Rec &r, uint32_t mask, uint8_t *d, const uint8_t *P = nullptr,
+                         uint32_t pn = GM_NONE) {
     const uint64_t args = r.base + r.uri_len, hdrs = args + r.args_len, body = hdrs + r.hdr_len;
     uint32_t a = 0, b = 0;
     if (mask & (DEC_PERCENT | DEC_URLENC)) {
@@ -177,37 +203,29 @@ __device__ uint2 dec_one(const uint8_t *A, const Rec &r, uint32_t mask, uint8_t 
     if (mask & DEC_BASE64) a += dec_b64(A + args, r.args_len, d ? d + a : nullptr);
     uint8_t *db = d ? d + a : nullptr;
     const uint32_t kind = (mask & (DEC_PERCENT | DEC_URLENC | DEC_JSON)) ? body_kind(A, r, hdrs) : 0u;
-    if (kind == 1 && (mask & (DEC_PERCENT | DEC_URLENC))) {
-        bool chg = false;
-        const uint32_t k = dec_form(A + body, r.body_len, mask, nullptr, chg);
-        if (chg) {
-            if (db) { dec_form(A + body, r.body_len, mask, db, chg); db[k] = '\n'; }
-            b += k + 1;
-        }
-    } else if (kind == 2 && (mask & DEC_JSON)) {
-        bool chg = false;
-        const uint32_t k = dec_json(A + body, r.body_len, nullptr, chg);
-        if (chg) {
-            if (db) { dec_json(A + body, r.body_len, db, chg); db[k] = '\n'; }
-            b += k + 1;
-        }
+    b = dec_body(A + body, r.body_len, kind, mask, db, b);
+    if (pn != GM_NONE) {
+        if (db) { for (uint32_t k = 0; k < pn; k++) db[b + k] = P[k]; db[b + pn] = '\n'; }
+        b = dec_body(P, pn, kind, mask, db, b + pn + 1);
     }
-    if (mask & DEC_BASE64) b += dec_b64(A + body, r.body_len, db ? db + b : nullptr);
     return make_uint2(a, b);
 }
 
 __device__ __forceinline__ uint32_t dec_mask_of(const gm_verdict &v, const GTab &t) {
     if (!waf_active(v) || v.location_id >= t.n_locs) return 0;
-    return (t.loc_uri[v.location_id].flags >> LOCURI_DEC_SHIFT) & 15u;
+    return (t.loc_uri[v.location_id].flags >> LOCURI_DEC_SHIFT) & 31u;
 }
 
 __global__ void k_dec_size(const gm_req *__restrict__ reqs, const uint8_t *__restrict__ A, uint32_t n, GTab t,
-                           const gm_verdict *__restrict__ out, uint64_t *__restrict__ sizes) {
+                           const gm_verdict *__restrict__ out, uint64_t *__restrict__ sizes,
+                           const uint8_t *__restrict__ Z, const uint64_t *__restrict__ zoff,
+                           const uint32_t *__restrict__ zlen) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t mask = dec_mask_of(out[i], t);
         uint64_t sz = 0;
         if (mask) {
-            const uint2 ab = dec_one(A, load_rec(reqs + i), mask, nullptr);
+            const bool gz = Z && (mask & DEC_GZIP);
+            const uint2 ab = dec_one(A, load_rec(reqs + i), mask, nullptr, gz ? Z + zoff[i] : nullptr, gz ? zlen[i] : GM_NONE);
             sz = ((uint64_t)ab.x + ab.y + 15) & ~15ull;
         }
         sizes[i] = sz;
@@ -220,7 +238,8 @@ __global__ void k_dec_emit(const gm_req *__restrict__ reqs, const uint8_t *__res
                            const gm_verdict *__restrict__ out, const uint64_t *__restrict__ base,
                            gm_req *__restrict__ sreqs, uint8_t *__restrict__ SA, uint64_t cap,
                            uint32_t *__restrict__ blk2rec, uint32_t nblk, uint64_t *__restrict__ len_dev,
-                           uint32_t *__restrict__ status) {
+                           uint32_t *__restrict__ status, const uint8_t *__restrict__ Z,
+                           const uint64_t *__restrict__ zoff, const uint32_t *__restrict__ zlen) {
     const uint64_t total = base[n];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *len_dev = min(total, cap);
@@ -234,7 +253,8 @@ __global__ void k_dec_emit(const gm_req *__restrict__ reqs, const uint8_t *__res
         const uint32_t mask = dec_mask_of(out[i], t);
         if (mask && sz && b + sz <= cap) {
             const Rec r = load_rec(reqs + i);
-            const uint2 ab = dec_one(A, r, mask, SA + b);
+            const bool gz = Z && (mask & DEC_GZIP);
+            const uint2 ab = dec_one(A, r, mask, SA + b, gz ? Z + zoff[i] : nullptr, gz ? zlen[i] : GM_NONE);
             s.args_len = ab.x; s.body_len = ab.y;
             for (uint64_t k = b + ab.x + ab.y; k < b + sz; k++) SA[k] = 0;   // the slot's alignment tail
         }

@@ -1683,6 +1683,7 @@ __global__ __launch_bounds__(ROUTE_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE
 #include "gm_waf.inc"
 #include "gm_rloc.inc"
 #include "gm_decode.inc"
+#include "gm_inflate.inc"
 
 }  // namespace
 
@@ -1767,6 +1768,15 @@ struct Scratch {
     uint64_t *d_ssize = nullptr, *d_sbase = nullptr; size_t cap_ssize = 0, cap_sbase = 0;
     uint8_t *d_stemp = nullptr; size_t cap_stemp = 0;
     uint8_t *d_utemp = nullptr; size_t cap_utemp = 0;
+    // gzip bodies (gm_inflate.inc): slot sizes, the members' list, control words, scan temp; the
+    // match path's slot offsets, lengths and inflated bytes (only for a generation with DEC_GZIP)
+    uint64_t *d_zlim = nullptr; size_t cap_zlim = 0;
+    uint32_t *d_zlist = nullptr; size_t cap_zlist = 0;
+    uint32_t *d_zctl = nullptr; size_t cap_zctl = 0;
+    uint8_t *d_ztemp = nullptr; size_t cap_ztemp = 0;
+    uint64_t *d_zoff = nullptr; size_t cap_zoff = 0;
+    uint32_t *d_zlen = nullptr; size_t cap_zlen = 0;
+    uint8_t *d_zout = nullptr; size_t cap_zout = 0;
     uint2 *d_rq = nullptr; size_t cap_rq = 0;            // regex-location requests deferred to k_rloc
     int32_t *d_rql = nullptr; size_t cap_rql = 0;        // and k_rloc's locations
     uint4 *d_rqs = nullptr; size_t cap_rqs = 0;          // and each one's $uri span + server (k_rloc_multi)
@@ -1821,7 +1831,9 @@ struct Scratch {
                         (void *)d_ssize, (void *)d_sbase, (void *)d_stemp, (void *)d_rq, (void *)d_rql, (void *)d_rqs, (void *)d_rqb, (void *)d_rqm, (void *)d_rqu, (void *)d_bctr, (void *)d_slow,
                         (void *)d_redo, (void *)d_rlist, (void *)d_rsize, (void *)d_rbase, (void *)d_rtemp, (void *)d_rsreq,
                         (void *)d_rsarena, (void *)d_rsout, (void *)d_rsblk, (void *)d_rscnt, (void *)d_ovlog, (void *)d_wmsg, (void *)d_spill, (void *)d_spill2,
-                        (void *)d_hlist, (void *)d_hcnt, (void *)d_along, (void *)d_amlist, (void *)d_amcnt})
+                        (void *)d_hlist, (void *)d_hcnt, (void *)d_along, (void *)d_amlist, (void *)d_amcnt,
+                        (void *)d_zlim, (void *)d_zlist, (void *)d_zctl, (void *)d_ztemp, (void *)d_zoff, (void *)d_zlen,
+                        (void *)d_zout})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
         if (h_ovlog) (void)hipHostFree(h_ovlog);
@@ -1918,6 +1930,7 @@ struct gm_ctx {
     std::atomic<uint32_t> n_set_reruns{0};    // gm_sync re-runs of OV_SET batches
     std::atomic<uint32_t> last_redo{0};       // requests the last continuation redid
     std::atomic<uint32_t> last_spill{0};      // pairs the last spill continuation emitted from the spill
+    std::atomic<uint32_t> last_inflated{0};   // gzip bodies given a view in the last batch
     std::shared_mutex gen_mu;                 // shared: enqueueing batches; exclusive: the swap
     Generation *gen = nullptr;
     uint64_t publish_seq = 0;                 // bumped under gen_mu (exclusive) by every publish
@@ -2254,6 +2267,7 @@ int gm_stats(gm_ctx *c, gm_stats_t *out) {
     out->n_set_reruns = c->n_set_reruns.load();
     out->last_redo = c->last_redo.load();
     out->last_spill = c->last_spill.load();
+    out->last_inflated = c->last_inflated.load();
     out->set_shift = c->set_shift;
     std::lock_guard<std::mutex> l2(c->last_mu);
     out->last_candidates = c->last_candidates;
@@ -2360,6 +2374,7 @@ struct WafIO {
     const gm_verdict *out;     // verdicts (waf_active, the decoders' location)
     const uint32_t *blk2rec;   // arena block -> first record (the route writes the batch's)
     uint32_t nblk;
+    uint32_t *infl_views = nullptr;   // the batch's count of inflated views (nullptr: a redo pass, not counted)
 };
 #ifndef GM_EXACT_BPC
 #define GM_EXACT_BPC 6
@@ -2432,6 +2447,36 @@ static int next_epoch(gm_ctx *c, Scratch *S, const GTab &t) {
         S->epoch = 1;
         HIPCHK(c, hipMemsetAsync(S->d_set, 0, S->cap_set * 8, S->stream));
     }
+    return GM_OK;
+}
+
+// The gzip stage (gm_inflate.inc): slot sizes and the members' list, one exclusive scan, the
+// persistent inflate kernel.  verdicts + t: only the requests whose location runs the parser
+// (nullptr: every request).  views: the device word that counts the bodies given a view (nullptr:
+// not kept); ov: the word that takes the out_cap overflow bit.
+static int launch_inflate(gm_ctx *c, Scratch *S, const gm_req *reqs, const uint8_t *A, uint64_t alen, const uint64_t *dlen,
+                          uint32_t n, const gm_verdict *verdicts, const GTab *t, uint8_t *out, uint64_t out_cap,
+                          uint64_t *off, uint32_t *len, uint32_t *views, uint32_t *ov) {
+    hipStream_t s = S->stream;
+    int e;
+    if ((e = grow(c, s, S->d_zlim, S->cap_zlim, (size_t)n + 1))) return e;
+    if ((e = grow(c, s, S->d_zlist, S->cap_zlist, (size_t)n))) return e;
+    if ((e = grow(c, s, S->d_zctl, S->cap_zctl, (size_t)INFL_CTL_WORDS))) return e;
+    size_t tb = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, S->d_zlim, off, (int)n, s));
+    if ((e = grow(c, s, S->d_ztemp, S->cap_ztemp, tb))) return e;
+    k_infl_reset<<<1, 64, 0, s>>>(S->d_zctl);
+    HIPCHK(c, hipGetLastError());
+    const uint32_t sblocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, (uint32_t)c->cu_count * 8));
+    k_infl_size<<<sblocks, 256, 0, s>>>(reqs, A, alen, dlen, n, verdicts, t ? t->loc_uri : nullptr, t ? t->n_locs : 0u,
+                                        S->d_zlim, len, S->d_zlist, S->d_zctl);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_ztemp, tb, S->d_zlim, off, (int)n, s));
+    // 8 workgroups of 4 waves per CU: the symbol loop is a dependent chain, occupancy hides it
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + INFL_WAVES - 1) / INFL_WAVES, (uint32_t)c->cu_count * 8));
+    k_inflate<<<blocks, INFL_BLOCK, 0, s>>>(reqs, A, n, S->d_zlist, S->d_zctl, out, out_cap, off, len,
+                                            views ? views : S->d_zctl + 2, ov ? ov : S->d_zctl + 3);
+    HIPCHK(c, hipGetLastError());
     return GM_OK;
 }
 
@@ -2510,7 +2555,20 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
     if (!t.decoders) return GM_OK;
     // ---- the request parsers' decoded views (gm_decode.inc): shadow records, same indices,
     // then the WAF stages once more over them; hits land in the same dedupe set and counts
-    const size_t scap = 2 * (size_t)io.alen + 32 * (size_t)n + 4096;   // a view <= 2x its zones
+    // (with the gzip parser: an inflated body P adds P, its transform and its base64 runs, <= 3 |P| + 2,
+    // and the batch's |P| sum to <= GM_INFLATE_RATIO * the arena)
+    const bool gzip = t.decoders & DEC_GZIP;
+    const size_t zcap = gzip ? (size_t)GM_INFLATE_RATIO * (size_t)io.alen + 16 : 0;
+    const size_t scap = 2 * (size_t)io.alen + 32 * (size_t)n + 4096 + 3 * zcap;   // a view <= 2x its zones
+    if (gzip) {
+        if ((e = grow(c, s, S->d_zout, S->cap_zout, zcap))) return e;
+        if ((e = grow(c, s, S->d_zoff, S->cap_zoff, (size_t)n))) return e;
+        if ((e = grow(c, s, S->d_zlen, S->cap_zlen, (size_t)n))) return e;
+        if ((e = launch_inflate(c, S, io.reqs, io.A, io.alen, io.dlen, n, io.out, &t, S->d_zout, zcap, S->d_zoff, S->d_zlen,
+                                io.infl_views, nullptr)))
+            return e;
+    }
+    const uint8_t *Z = gzip ? S->d_zout : nullptr;
     const uint32_t snblk = (uint32_t)((scap >> BLK_SHIFT) + 1);
     if ((e = grow(c, s, S->d_sreqs, S->cap_sreqs, (size_t)n))) return e;
     if ((e = grow(c, s, S->d_sarena, S->cap_sarena, scap))) return e;
@@ -2521,12 +2579,12 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, dtmp, S->d_ssize, S->d_sbase, (int)n + 1, s));
     if ((e = grow(c, s, S->d_stemp, S->cap_stemp, dtmp))) return e;
     const uint32_t dblocks = (n + 255) / 256;
-    k_dec_size<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_ssize);
+    k_dec_size<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_ssize, Z, S->d_zoff, S->d_zlen);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_stemp, dtmp, S->d_ssize, S->d_sbase, (int)n + 1, s));
     uint64_t *slen = S->d_sbase + n + 1;   // the shadow arena's length, on the device
     k_dec_emit<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_sbase, S->d_sreqs, S->d_sarena, scap,
-                                       S->d_sblk, snblk, slen, S->d_status);
+                                       S->d_sblk, snblk, slen, S->d_status, Z, S->d_zoff, S->d_zlen);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(S->d_status + 2, 0, 4, s));   // the job list restarts (pairs continue)
     k_status_pass<<<1, 64, 0, s>>>(S->d_status);   // the continuations restart too
@@ -2770,7 +2828,7 @@ static int run_batch(gm_ctx *c, Scratch *S, const Generation *g, const gm_req *r
     };
     if (serial && (e = launch_route())) return e;
     if (mark(1)) return GM_E_HIP;
-    const WafIO io{A, alen, dlen, reqs, n, out, S->d_blk2rec, nblk};
+    const WafIO io{A, alen, dlen, reqs, n, out, S->d_blk2rec, nblk, S->d_status + INFL_VIEWS_WORD};
     if ((e = waf_stages(c, S, g, k, io, dd, serial ? std::function<int()>() : std::function<int()>(launch_route), !serial,
                         mark))) return e;
     // ---- hit emission: offsets by an exclusive scan of the per-request counts (request order)
@@ -3022,6 +3080,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
         c->last_jobs = S->h_status[2];
         c->last_pairs = S->h_status[1];
         c->last_hits = S->h_status[4];
+        c->last_inflated = S->h_status[INFL_VIEWS_WORD];
         if (S->ev_pending) {
             for (int k = 0; k < 4; k++) {
                 c->last_ms[k] = 0;
@@ -3033,6 +3092,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
         }
     }
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
+    const uint32_t infl_ov = S->h_status[INFL_STATUS_WORD];
     std::vector<Scratch::Replay> pend;
     pend.swap(S->pending);
     const bool last_in_place = S->last_is_batch;
@@ -3071,6 +3131,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     for (uint32_t ov : ovs) S->sync_log.push_back((ov & (OV_HITS | OV_DEC)) || ov_held(ov) ? GM_E_OVERFLOW : GM_OK);
     if (parse_ov) return fail(c, GM_E_OVERFLOW, "gm_parse_requests: arena capacity exceeded");
     if (upuri_ov) return fail(c, GM_E_OVERFLOW, "gm_upstream_uris: output capacity exceeded");
+    if (infl_ov) return fail(c, GM_E_OVERFLOW, "gm_inflate_bodies: output capacity exceeded");
     if (err & OV_HITS) return fail(c, GM_E_OVERFLOW, "hit_ids capacity exceeded (the batch's counters were not committed)");
     // candidate / survivor / pair / job overflows were completed on the device (k_waf_direct, the
     // set-based scatter and regex runs): the batch is whole, the buffers grow for speed
@@ -3173,7 +3234,7 @@ int gm_sync_batches(gm_ctx *c, void *stream, int32_t *status, size_t cap) {
     const int e = sync_pending(c, S);
     if (e && e != GM_E_OVERFLOW) return e;   // (a HIP error: the log stays for the next call)
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
-    if (e && (parse_ov || upuri_ov)) return e;   // not a gm_match_batch's: reported as gm_sync does
+    if (e && (parse_ov || upuri_ov || S->h_status[INFL_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
     const size_t n = S->sync_log.size();
     for (size_t i = 0; i < n && i < cap; i++) status[i] = S->sync_log[i];
     S->sync_log.clear();
@@ -3920,6 +3981,37 @@ extern "C" int gm_upstream_uris(gm_ctx *c, const gm_batch *in, const gm_verdict 
                                         S->d_status + UPURI_STATUS_WORD);
     HIPCHK(c, hipGetLastError());
     return G.done(c);
+}
+
+// ---------------------------------------------------------------- gzip request bodies (§8 f4)
+extern "C" int gm_inflate_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                 uint32_t *out_len, void *stream) {
+    if (!c || !in) return fail(c, GM_E_INVAL, "null argument");
+    if (c->flags & GM_CREATE_COMPILE_ONLY) return fail(c, GM_E_NODEVICE, "compile-only context");
+    if (in->flags & GM_BATCH_HOST) return fail(c, GM_E_INVAL, "gm_inflate_bodies takes device buffers");
+    const uint32_t n = in->n;
+    if (n && (!out_off || !out_len || !in->reqs || !in->arena || (!out && out_cap))) return fail(c, GM_E_INVAL, "null argument");
+    if ((uintptr_t)in->reqs & 15) return fail(c, GM_E_INVAL, "reqs must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t s = (hipStream_t)stream;
+    Scratch *S = scratch_for(c, s);
+    if (!S) return fail(c, GM_E_NOMEM, t_err);
+    DoneGuard G(S);
+    HIPCHK(c, hipMemsetAsync(S->d_status + INFL_STATUS_WORD, 0, 4, s));
+    if (n == 0) return GM_OK;
+    if (int e = launch_inflate(c, S, in->reqs, in->arena, in->arena_len, in->arena_len_dev, n, nullptr, nullptr, out, out_cap,
+                               out_off, out_len, nullptr, S->d_status + INFL_STATUS_WORD))
+        return e;
+    return G.done(c);
+}
+
+// The request parsers location `loc` of the live generation runs (GM_DEC_* bits), < 0: no such location.
+extern "C" int gm_debug_loc_decoders(gm_ctx *c, uint32_t loc) {
+    if (!c || !c->gen) return -1;
+    const TabHeader &h = c->gen->hdr;
+    if (loc >= h.n_locs) return -1;
+    const DLocUri *lu = reinterpret_cast<const DLocUri *>(c->gen->host_image.data() + h.off_loc_uri);
+    return (int)((lu[loc].flags >> LOCURI_DEC_SHIFT) & 31u);
 }
 
 // The measurement / tuning variants compiled in (gm_stats_t.build_flags): a bench line can show it

@@ -35,8 +35,9 @@ class Rule:
 
 
 class SigSet:
-    """``decoders``: the request parsers (Wallarm's names: percent, urlenc, json_doc, base64) whose
-    decoded views of $args / the body the rules also scan ("@decoders" line, gm_decode.inc)."""
+    """``decoders``: the request parsers (Wallarm's names: percent, urlenc, json_doc, base64, gzip)
+    whose decoded views of $args / the body the rules also scan ("@decoders" line, gm_decode.inc;
+    gzip: a body that is a gzip member, inflated on the device, gm_inflate.inc)."""
 
     def __init__(self, rules, decoders=()):
         self.rules = list(rules)
