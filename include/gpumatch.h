@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 11u  /* 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
+#define GM_ABI_VERSION 12u  /* 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
                                7: GM_ACT_TOO_LARGE, GM_REQ_CHUNKED, gm_rejects, build flags; 6: n_rsl_reversed;
                                5: gm_update_upstream / gm_peers_migrate; 4: union-DFA stats */
 
@@ -264,6 +264,9 @@ typedef struct gm_stats_t {
      * the files of ingress-plus_amd/csrc and include/gpumatch.h, first 16 hex digits as a number; 0 = unknown):
      * a profile or bench line names the build it measured, not the tree beside it */
     uint64_t csrc_hash;
+    /* multipart bodies given a part view in the last batch (GM_DEC_MULTIPART) */
+    uint32_t last_multipart;
+    uint32_t reserved1;
 } gm_stats_t;
 
 /* gm_stats_t.build_flags: measurement / test variants compiled into the library.  bench.py refuses
@@ -281,12 +284,16 @@ typedef struct gm_stats_t {
  *   base64    every run of >= 16 base64 characters in $args / the body, decoded
  *   gzip      a body that is a gzip member (1f 8b 08 ..., whatever Content-Encoding says), inflated
  *             (gm_inflate_bodies below); the view, its form / JSON transform by the body's
- *             Content-Type and its base64 runs are scanned after the raw body's parts */
+ *             Content-Type and its base64 runs are scanned after the raw body's parts
+ *   multipart a multipart/form-data body's part view M (gm_multipart_bodies below: names, filenames
+ *             and the part contents with base64 / quoted-printable undone); M, its JSON unescape if
+ *             a part is JSON, and its base64 runs are scanned after everything above */
 #define GM_DEC_PERCENT 0x1u
 #define GM_DEC_URLENC  0x2u
 #define GM_DEC_JSON    0x4u
 #define GM_DEC_BASE64  0x8u
 #define GM_DEC_GZIP    0x10u
+#define GM_DEC_MULTIPART 0x20u
 
 typedef struct gm_ctx gm_ctx;
 
@@ -442,6 +449,44 @@ int         gm_upstream_uris(gm_ctx *ctx, const gm_batch *in, const gm_verdict *
  * signature set that declares `gzip`. */
 int         gm_inflate_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
                               uint64_t *out_off, uint32_t *out_len, void *stream);
+
+/* ---------------------------------------------------------------- multipart request bodies
+ * (Wallarm's `multipart` parser.)  The part view M of every multipart body, a wave
+ * per body (gm_multipart.inc states the same grammar beside the kernel):
+ *  - Which bodies: the request's first Content-Type value starts with "multipart/" (ASCII
+ *    case-insensitive); after its first ';' the first case-insensitive "boundary=" preceded by ';',
+ *    space or tab; B is the bytes up to the next '"' (or the value's end) if a '"' follows, else up
+ *    to the first ';', space, tab or the value's end; 1 <= |B| <= 70.  The body is read as sent.
+ *  - Delimiter: D = "--" B at body offset 0 or directly after '\n', followed by "--" (close: the rest
+ *    is ignored) or by a run of space, tab, '\r' and then '\n' (a part begins after it).  Anything else
+ *    is content.  Bytes before the first delimiter are ignored; no delimiter: no view; no close
+ *    delimiter: the last part runs to the body's end.
+ *  - A part: the bytes up to the next D minus one trailing '\n', then one trailing '\r'.  Lines end at
+ *    '\n' (a '\r' before it dropped); the headers end at the first empty line whose '\n' lies in the
+ *    part, the content follows; no empty line: no content.  No folding.  The part's first line of
+ *    each of (case-insensitive name and ':' at the line's start):
+ *      Content-Disposition: read left to right for "name=", "filename=", "filename*=" preceded by
+ *        ';', space or tab.  name / filename: a quoted string (to the next unescaped '"' or the
+ *        line's end; \x -> x) or a token (to ';', space, tab, '\r' or the line's end).  filename*=:
+ *        a token, the bytes after its second ''' percent-decoded (nothing with fewer than two).
+ *        The read resumes after each value; the first of each kind is taken.
+ *      Content-Type: the part is JSON if the value contains "json" (case-insensitive).
+ *      Content-Transfer-Encoding: the value without leading / trailing spaces and tabs equals
+ *        "base64" or "quoted-printable" (case-insensitive).
+ *    The first GM_MULTIPART_PARTS parts are taken, later ones ignored.
+ *  - M: per taken part, each of name, filename, decoded filename*, content (if the part has an empty
+ *    line) followed by '\n'.  Content under base64: bytes outside [A-Za-z0-9+/] skipped, each full
+ *    quantum decoded, a partial one ignored; under quoted-printable: "=XY" -> the byte, '=' before
+ *    "\r\n" or "\n" removed with it, any other byte kept; otherwise verbatim.
+ *  - |M| <= body_len (proof in gm_multipart.inc): request i's slot is body_len bytes.
+ * out_len[i] = |M| of request i's body at out[out_off[i]], out_flags[i] = taken parts << 8 | (a taken
+ * part is JSON); out_len[i] = GM_NONE (flags 0): not a multipart body, or one with no delimiter (or
+ * past out_cap: gm_sync then reports GM_E_OVERFLOW).  out_cap >= in->arena_len always suffices.
+ * Device pointers, asynchronous on `stream`, completed by gm_sync.  Needs no generation: the kernel
+ * gm_match_batch runs for a signature set that declares `multipart`. */
+#define GM_MULTIPART_PARTS 64
+int         gm_multipart_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_off, uint32_t *out_len, uint32_t *out_flags, void *stream);
 
 /* ---------------------------------------------------------------- upstream peer selection
  * (the step after the path.)  The upstream blocks the templates render

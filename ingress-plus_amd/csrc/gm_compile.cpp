@@ -132,6 +132,7 @@ uint32_t decoder_bit(const std::string &name) {
     if (name == "json_doc" || name == "json") return DEC_JSON;
     if (name == "base64") return DEC_BASE64;
     if (name == "gzip") return DEC_GZIP;
+    if (name == "multipart") return DEC_MULTIPART;
     return 0;
 }
 

@@ -1684,6 +1684,7 @@ __global__ __launch_bounds__(ROUTE_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE
 #include "gm_rloc.inc"
 #include "gm_decode.inc"
 #include "gm_inflate.inc"
+#include "gm_multipart.inc"
 
 }  // namespace
 
@@ -1777,6 +1778,17 @@ struct Scratch {
     uint64_t *d_zoff = nullptr; size_t cap_zoff = 0;
     uint32_t *d_zlen = nullptr; size_t cap_zlen = 0;
     uint8_t *d_zout = nullptr; size_t cap_zout = 0;
+    // multipart bodies (gm_multipart.inc): slot sizes, boundaries, the bodies' list, control words,
+    // scan temp; the match path's slot offsets, lengths, flags and views (only with DEC_MULTIPART)
+    uint64_t *d_mlim = nullptr; size_t cap_mlim = 0;
+    uint64_t *d_mbnd = nullptr; size_t cap_mbnd = 0;
+    uint32_t *d_mlist = nullptr; size_t cap_mlist = 0;
+    uint32_t *d_mctl = nullptr; size_t cap_mctl = 0;
+    uint8_t *d_mtemp = nullptr; size_t cap_mtemp = 0;
+    uint64_t *d_moff = nullptr; size_t cap_moff = 0;
+    uint32_t *d_mlen = nullptr; size_t cap_mlen = 0;
+    uint32_t *d_mflg = nullptr; size_t cap_mflg = 0;
+    uint8_t *d_mout = nullptr; size_t cap_mout = 0;
     uint2 *d_rq = nullptr; size_t cap_rq = 0;            // regex-location requests deferred to k_rloc
     int32_t *d_rql = nullptr; size_t cap_rql = 0;        // and k_rloc's locations
     uint4 *d_rqs = nullptr; size_t cap_rqs = 0;          // and each one's $uri span + server (k_rloc_multi)
@@ -1833,7 +1845,8 @@ struct Scratch {
                         (void *)d_rsarena, (void *)d_rsout, (void *)d_rsblk, (void *)d_rscnt, (void *)d_ovlog, (void *)d_wmsg, (void *)d_spill, (void *)d_spill2,
                         (void *)d_hlist, (void *)d_hcnt, (void *)d_along, (void *)d_amlist, (void *)d_amcnt,
                         (void *)d_zlim, (void *)d_zlist, (void *)d_zctl, (void *)d_ztemp, (void *)d_zoff, (void *)d_zlen,
-                        (void *)d_zout})
+                        (void *)d_zout, (void *)d_mlim, (void *)d_mbnd, (void *)d_mlist, (void *)d_mctl, (void *)d_mtemp,
+                        (void *)d_moff, (void *)d_mlen, (void *)d_mflg, (void *)d_mout})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
         if (h_ovlog) (void)hipHostFree(h_ovlog);
@@ -1931,6 +1944,7 @@ struct gm_ctx {
     std::atomic<uint32_t> last_redo{0};       // requests the last continuation redid
     std::atomic<uint32_t> last_spill{0};      // pairs the last spill continuation emitted from the spill
     std::atomic<uint32_t> last_inflated{0};   // gzip bodies given a view in the last batch
+    std::atomic<uint32_t> last_multipart{0};  // multipart bodies given a view in the last batch
     std::shared_mutex gen_mu;                 // shared: enqueueing batches; exclusive: the swap
     Generation *gen = nullptr;
     uint64_t publish_seq = 0;                 // bumped under gen_mu (exclusive) by every publish
@@ -2268,6 +2282,8 @@ int gm_stats(gm_ctx *c, gm_stats_t *out) {
     out->last_redo = c->last_redo.load();
     out->last_spill = c->last_spill.load();
     out->last_inflated = c->last_inflated.load();
+    out->last_multipart = c->last_multipart.load();
+    out->reserved1 = 0;
     out->set_shift = c->set_shift;
     std::lock_guard<std::mutex> l2(c->last_mu);
     out->last_candidates = c->last_candidates;
@@ -2375,6 +2391,7 @@ struct WafIO {
     const uint32_t *blk2rec;   // arena block -> first record (the route writes the batch's)
     uint32_t nblk;
     uint32_t *infl_views = nullptr;   // the batch's count of inflated views (nullptr: a redo pass, not counted)
+    uint32_t *mp_views = nullptr;     // and of multipart views
 };
 #ifndef GM_EXACT_BPC
 #define GM_EXACT_BPC 6
@@ -2480,6 +2497,36 @@ static int launch_inflate(gm_ctx *c, Scratch *S, const gm_req *reqs, const uint8
     return GM_OK;
 }
 
+// The multipart stage (gm_multipart.inc), launched as the gzip stage: slot sizes (the bodies'
+// lengths), boundaries and the bodies' list, one exclusive scan, the persistent wave-per-body kernel.
+// verdicts + t, views, ov: as launch_inflate's.
+static int launch_multipart(gm_ctx *c, Scratch *S, const gm_req *reqs, const uint8_t *A, uint64_t alen, const uint64_t *dlen,
+                            uint32_t n, const gm_verdict *verdicts, const GTab *t, uint8_t *out, uint64_t out_cap,
+                            uint64_t *off, uint32_t *len, uint32_t *flags, uint32_t *views, uint32_t *ov) {
+    hipStream_t s = S->stream;
+    int e;
+    if ((e = grow(c, s, S->d_mlim, S->cap_mlim, (size_t)n + 1))) return e;
+    if ((e = grow(c, s, S->d_mbnd, S->cap_mbnd, (size_t)n))) return e;
+    if ((e = grow(c, s, S->d_mlist, S->cap_mlist, (size_t)n))) return e;
+    if ((e = grow(c, s, S->d_mctl, S->cap_mctl, (size_t)MP_CTL_WORDS))) return e;
+    size_t tb = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, S->d_mlim, off, (int)n, s));
+    if ((e = grow(c, s, S->d_mtemp, S->cap_mtemp, tb))) return e;
+    k_mp_reset<<<1, 64, 0, s>>>(S->d_mctl);
+    HIPCHK(c, hipGetLastError());
+    const uint32_t sblocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, (uint32_t)c->cu_count * 8));
+    k_mp_size<<<sblocks, 256, 0, s>>>(reqs, A, alen, dlen, n, verdicts, t ? t->loc_uri : nullptr, t ? t->n_locs : 0u,
+                                      S->d_mlim, S->d_mbnd, len, flags, S->d_mlist, S->d_mctl);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_mtemp, tb, S->d_mlim, off, (int)n, s));
+    // 8 workgroups of 4 waves per CU: the loads of a wave's body are dependent steps, occupancy hides them
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + MP_WAVES - 1) / MP_WAVES, (uint32_t)c->cu_count * 8));
+    k_multipart<<<blocks, MP_BLOCK, 0, s>>>(reqs, A, n, S->d_mlist, S->d_mctl, S->d_mbnd, out, out_cap, off, len, flags,
+                                            views ? views : S->d_mctl + 2, ov ? ov : S->d_mctl + 3);
+    HIPCHK(c, hipGetLastError());
+    return GM_OK;
+}
+
 static int launch_scan(gm_ctx *c, Scratch *S, const GTab &t, const WafCaps &k, const uint8_t *A, uint64_t alen,
                        const uint64_t *dlen) {
     hipStream_t s = S->stream;
@@ -2559,7 +2606,10 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
     // and the batch's |P| sum to <= GM_INFLATE_RATIO * the arena)
     const bool gzip = t.decoders & DEC_GZIP;
     const size_t zcap = gzip ? (size_t)GM_INFLATE_RATIO * (size_t)io.alen + 16 : 0;
-    const size_t scap = 2 * (size_t)io.alen + 32 * (size_t)n + 4096 + 3 * zcap;   // a view <= 2x its zones
+    // (with the multipart parser: a view M, |M| <= its body, adds M, its JSON transform and its base64 runs)
+    const bool mpart = t.decoders & DEC_MULTIPART;
+    const size_t mcap = mpart ? (size_t)io.alen + 16 : 0;
+    const size_t scap = 2 * (size_t)io.alen + 32 * (size_t)n + 4096 + 3 * zcap + 3 * mcap;   // a view <= 2x its zones
     if (gzip) {
         if ((e = grow(c, s, S->d_zout, S->cap_zout, zcap))) return e;
         if ((e = grow(c, s, S->d_zoff, S->cap_zoff, (size_t)n))) return e;
@@ -2569,6 +2619,16 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
             return e;
     }
     const uint8_t *Z = gzip ? S->d_zout : nullptr;
+    if (mpart) {
+        if ((e = grow(c, s, S->d_mout, S->cap_mout, mcap))) return e;
+        if ((e = grow(c, s, S->d_moff, S->cap_moff, (size_t)n))) return e;
+        if ((e = grow(c, s, S->d_mlen, S->cap_mlen, (size_t)n))) return e;
+        if ((e = grow(c, s, S->d_mflg, S->cap_mflg, (size_t)n))) return e;
+        if ((e = launch_multipart(c, S, io.reqs, io.A, io.alen, io.dlen, n, io.out, &t, S->d_mout, mcap, S->d_moff, S->d_mlen,
+                                  S->d_mflg, io.mp_views, nullptr)))
+            return e;
+    }
+    const uint8_t *MV = mpart ? S->d_mout : nullptr;
     const uint32_t snblk = (uint32_t)((scap >> BLK_SHIFT) + 1);
     if ((e = grow(c, s, S->d_sreqs, S->cap_sreqs, (size_t)n))) return e;
     if ((e = grow(c, s, S->d_sarena, S->cap_sarena, scap))) return e;
@@ -2579,12 +2639,14 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, dtmp, S->d_ssize, S->d_sbase, (int)n + 1, s));
     if ((e = grow(c, s, S->d_stemp, S->cap_stemp, dtmp))) return e;
     const uint32_t dblocks = (n + 255) / 256;
-    k_dec_size<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_ssize, Z, S->d_zoff, S->d_zlen);
+    k_dec_size<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_ssize, Z, S->d_zoff, S->d_zlen, MV, S->d_moff, S->d_mlen,
+                                       S->d_mflg);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_stemp, dtmp, S->d_ssize, S->d_sbase, (int)n + 1, s));
     uint64_t *slen = S->d_sbase + n + 1;   // the shadow arena's length, on the device
     k_dec_emit<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_sbase, S->d_sreqs, S->d_sarena, scap,
-                                       S->d_sblk, snblk, slen, S->d_status, Z, S->d_zoff, S->d_zlen);
+                                       S->d_sblk, snblk, slen, S->d_status, Z, S->d_zoff, S->d_zlen, MV, S->d_moff,
+                                       S->d_mlen, S->d_mflg);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(S->d_status + 2, 0, 4, s));   // the job list restarts (pairs continue)
     k_status_pass<<<1, 64, 0, s>>>(S->d_status);   // the continuations restart too
@@ -2828,7 +2890,8 @@ static int run_batch(gm_ctx *c, Scratch *S, const Generation *g, const gm_req *r
     };
     if (serial && (e = launch_route())) return e;
     if (mark(1)) return GM_E_HIP;
-    const WafIO io{A, alen, dlen, reqs, n, out, S->d_blk2rec, nblk, S->d_status + INFL_VIEWS_WORD};
+    const WafIO io{A, alen, dlen, reqs, n, out, S->d_blk2rec, nblk, S->d_status + INFL_VIEWS_WORD,
+                   S->d_status + MP_VIEWS_WORD};
     if ((e = waf_stages(c, S, g, k, io, dd, serial ? std::function<int()>() : std::function<int()>(launch_route), !serial,
                         mark))) return e;
     // ---- hit emission: offsets by an exclusive scan of the per-request counts (request order)
@@ -3081,6 +3144,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
         c->last_pairs = S->h_status[1];
         c->last_hits = S->h_status[4];
         c->last_inflated = S->h_status[INFL_VIEWS_WORD];
+        c->last_multipart = S->h_status[MP_VIEWS_WORD];
         if (S->ev_pending) {
             for (int k = 0; k < 4; k++) {
                 c->last_ms[k] = 0;
@@ -3092,7 +3156,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
         }
     }
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
-    const uint32_t infl_ov = S->h_status[INFL_STATUS_WORD];
+    const uint32_t infl_ov = S->h_status[INFL_STATUS_WORD], mp_ov = S->h_status[MP_STATUS_WORD];
     std::vector<Scratch::Replay> pend;
     pend.swap(S->pending);
     const bool last_in_place = S->last_is_batch;
@@ -3132,6 +3196,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     if (parse_ov) return fail(c, GM_E_OVERFLOW, "gm_parse_requests: arena capacity exceeded");
     if (upuri_ov) return fail(c, GM_E_OVERFLOW, "gm_upstream_uris: output capacity exceeded");
     if (infl_ov) return fail(c, GM_E_OVERFLOW, "gm_inflate_bodies: output capacity exceeded");
+    if (mp_ov) return fail(c, GM_E_OVERFLOW, "gm_multipart_bodies: output capacity exceeded");
     if (err & OV_HITS) return fail(c, GM_E_OVERFLOW, "hit_ids capacity exceeded (the batch's counters were not committed)");
     // candidate / survivor / pair / job overflows were completed on the device (k_waf_direct, the
     // set-based scatter and regex runs): the batch is whole, the buffers grow for speed
@@ -3234,7 +3299,7 @@ int gm_sync_batches(gm_ctx *c, void *stream, int32_t *status, size_t cap) {
     const int e = sync_pending(c, S);
     if (e && e != GM_E_OVERFLOW) return e;   // (a HIP error: the log stays for the next call)
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
-    if (e && (parse_ov || upuri_ov || S->h_status[INFL_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
+    if (e && (parse_ov || upuri_ov || S->h_status[INFL_STATUS_WORD] || S->h_status[MP_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
     const size_t n = S->sync_log.size();
     for (size_t i = 0; i < n && i < cap; i++) status[i] = S->sync_log[i];
     S->sync_log.clear();
@@ -4005,13 +4070,36 @@ extern "C" int gm_inflate_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, ui
     return G.done(c);
 }
 
+// ---------------------------------------------------------------- multipart request bodies (§8 f4)
+extern "C" int gm_multipart_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                   uint32_t *out_len, uint32_t *out_flags, void *stream) {
+    if (!c || !in) return fail(c, GM_E_INVAL, "null argument");
+    if (c->flags & GM_CREATE_COMPILE_ONLY) return fail(c, GM_E_NODEVICE, "compile-only context");
+    if (in->flags & GM_BATCH_HOST) return fail(c, GM_E_INVAL, "gm_multipart_bodies takes device buffers");
+    const uint32_t n = in->n;
+    if (n && (!out_off || !out_len || !out_flags || !in->reqs || !in->arena || (!out && out_cap)))
+        return fail(c, GM_E_INVAL, "null argument");
+    if ((uintptr_t)in->reqs & 15) return fail(c, GM_E_INVAL, "reqs must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t s = (hipStream_t)stream;
+    Scratch *S = scratch_for(c, s);
+    if (!S) return fail(c, GM_E_NOMEM, t_err);
+    DoneGuard G(S);
+    HIPCHK(c, hipMemsetAsync(S->d_status + MP_STATUS_WORD, 0, 4, s));
+    if (n == 0) return GM_OK;
+    if (int e = launch_multipart(c, S, in->reqs, in->arena, in->arena_len, in->arena_len_dev, n, nullptr, nullptr, out, out_cap,
+                                 out_off, out_len, out_flags, nullptr, S->d_status + MP_STATUS_WORD))
+        return e;
+    return G.done(c);
+}
+
 // The request parsers location `loc` of the live generation runs (GM_DEC_* bits), < 0: no such location.
 extern "C" int gm_debug_loc_decoders(gm_ctx *c, uint32_t loc) {
     if (!c || !c->gen) return -1;
     const TabHeader &h = c->gen->hdr;
     if (loc >= h.n_locs) return -1;
     const DLocUri *lu = reinterpret_cast<const DLocUri *>(c->gen->host_image.data() + h.off_loc_uri);
-    return (int)((lu[loc].flags >> LOCURI_DEC_SHIFT) & 31u);
+    return (int)((lu[loc].flags >> LOCURI_DEC_SHIFT) & 63u);
 }
 
 // The measurement / tuning variants compiled in (gm_stats_t.build_flags): a bench line can show it
