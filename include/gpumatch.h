@@ -49,7 +49,12 @@ extern "C" {
 #define GM_E_EARLIER   -10   /* gm_match_batch: an EARLIER batch of the stream completed void in the
                                 sync this call forced (PENDING_MAX unsynced batches, or a GM_BATCH_HOST
                                 batch behind device ones); this batch was not enqueued.
-                                gm_sync_batches names the void batch(es) */
+                                gm_sync_batches names the void batch(es).  Returned only when a
+                                batch that sync completed is void: any other outcome of the forced
+                                sync comes back as gm_sync reports it (GM_E_OVERFLOW for a
+                                gm_parse_requests / gm_upstream_uris / gm_inflate_bodies /
+                                gm_multipart_bodies capacity overflow: every batch is whole, and
+                                this one was not enqueued either) */
 
 /* ---------------------------------------------------------------- gm_create flags */
 #define GM_CREATE_COMPILE_ONLY  0x1u  /* no HIP device: compile + stats only (host tests) */
@@ -337,8 +342,9 @@ int         gm_sync(gm_ctx *ctx, void *stream);
  * counters were not committed: retry it, and only it) for every batch completed since the previous
  * gm_sync / gm_sync_batches on the stream, forced completions included, in enqueue order; it
  * returns that number of batches (entries past `cap` are not written), or a negative GM_E_* for an
- * error no batch status describes (HIP; gm_parse_requests / gm_upstream_uris capacity, which gm_sync
- * reports the same way; the statuses are then kept for the next call).  gm_sync discards them. */
+ * error no batch status describes (HIP; gm_parse_requests / gm_upstream_uris / gm_inflate_bodies /
+ * gm_multipart_bodies capacity, which gm_sync reports the same way, once: the sync that reports it
+ * clears it; the statuses are then kept for the next call).  gm_sync discards them. */
 int         gm_sync_batches(gm_ctx *ctx, void *stream, int32_t *status, size_t cap);
 
 /* Per-location and per-signature hit counters of this device, u64, cumulative since the

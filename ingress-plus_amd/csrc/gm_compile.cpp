@@ -1926,8 +1926,11 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
             } else if (L.stub) dl.kind = LK_STATUS;
             else dl.kind = LK_NONE;
             // the access phase beside the Wallarm module's (both in NGX_HTTP_ACCESS_PHASE, in an
-            // order the reference does not fix): a location with both defers
-            if (dl.access != GM_NONE && dl.waf_mode != GM_WAF_OFF && dl.kind != LK_RETURN && dl.kind != LK_UNSUPPORTED) {
+            // order the reference does not fix): a location with both defers.  A `return` location
+            // answers in the rewrite phase and never reaches either -- a route location's `return
+            // 418` too: the named target it redirects to is judged instead (route_loc)
+            if (dl.access != GM_NONE && dl.waf_mode != GM_WAF_OFF && dl.kind != LK_RETURN && dl.kind != LK_UNSUPPORTED &&
+                dl.kind != LK_IRL_RULES && dl.kind != LK_IRL_SPLIT) {
                 dl.kind = LK_UNSUPPORTED; st.n_rejected_other++;
                 R.rejects.push_back("location " + L.path + ": allow / deny beside wallarm_mode");
             }

@@ -3193,6 +3193,12 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     }
     // (the same conditions as the batch-void errors below, per batch)
     for (uint32_t ov : ovs) S->sync_log.push_back((ov & (OV_HITS | OV_DEC)) || ov_held(ov) ? GM_E_OVERFLOW : GM_OK);
+    // a capacity overflow of the stream's other calls is no batch's: this sync reports it, once (its
+    // status word is cleared, so the next sync hands out the batch statuses kept in sync_log)
+    if (parse_ov) HIPCHK(c, hipMemsetAsync(S->d_status + PARSE_STATUS_WORD + 3, 0, 4, S->stream));
+    if (upuri_ov) HIPCHK(c, hipMemsetAsync(S->d_status + UPURI_STATUS_WORD, 0, 4, S->stream));
+    if (infl_ov) HIPCHK(c, hipMemsetAsync(S->d_status + INFL_STATUS_WORD, 0, 4, S->stream));
+    if (mp_ov) HIPCHK(c, hipMemsetAsync(S->d_status + MP_STATUS_WORD, 0, 4, S->stream));
     if (parse_ov) return fail(c, GM_E_OVERFLOW, "gm_parse_requests: arena capacity exceeded");
     if (upuri_ov) return fail(c, GM_E_OVERFLOW, "gm_upstream_uris: output capacity exceeded");
     if (infl_ov) return fail(c, GM_E_OVERFLOW, "gm_inflate_bodies: output capacity exceeded");
@@ -3206,6 +3212,21 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     return GM_OK;
 }
 
+// The sync a gm_match_batch forces on its stream: GM_E_EARLIER when one of the batches it completed
+// is void (a GM_E_OVERFLOW among the sync_log entries it added; gm_sync_batches names it).  Any
+// other outcome is returned as gm_sync reports it -- a gm_parse_requests / gm_upstream_uris /
+// gm_inflate_bodies / gm_multipart_bodies capacity overflow is GM_E_OVERFLOW with every batch whole.
+static int forced_sync(gm_ctx *c, Scratch *S, const char *where) {
+    const size_t n0 = S->sync_log.size();
+    const int e0 = sync_pending(c, S);
+    if (e0 != GM_E_OVERFLOW) return e0;
+    bool earlier = false;
+    for (size_t i = n0; i < S->sync_log.size(); i++) earlier |= S->sync_log[i] == GM_E_OVERFLOW;
+    if (!earlier) return e0;
+    return fail(c, GM_E_EARLIER, std::string("an earlier batch of this stream completed void ") + where + " (" + t_err +
+                                 "); this batch was not enqueued");
+}
+
 int gm_match_batch(gm_ctx *c, const gm_batch *in, gm_verdict *out, uint32_t *hit_ids, size_t hit_cap, void *stream) {
     if (!c || !in || !out) return fail(c, GM_E_INVAL, "null argument");
     if (c->flags & GM_CREATE_COMPILE_ONLY) return fail(c, GM_E_NODEVICE, "compile-only context");
@@ -3216,10 +3237,7 @@ int gm_match_batch(gm_ctx *c, const gm_batch *in, gm_verdict *out, uint32_t *hit
     // the stream's pending batches are recorded until gm_sync; past PENDING_MAX unsynced batches the
     // oldest are completed here first (synchronously), so no batch's overflow goes unreported
     if (S->pending.size() >= PENDING_MAX) {
-        const int e0 = sync_pending(c, S);
-        if (e0 == GM_E_OVERFLOW)
-            return fail(c, GM_E_EARLIER, "an earlier batch of this stream completed void in the forced sync (" +
-                                         t_err + "); this batch was not enqueued");
+        const int e0 = forced_sync(c, S, "in the forced sync");
         if (e0) return e0;
     }
     std::shared_lock<std::shared_mutex> lk(c->gen_mu);
@@ -3247,10 +3265,7 @@ int gm_match_batch(gm_ctx *c, const gm_batch *in, gm_verdict *out, uint32_t *hit
     // host buffers: stage reqs + arena + verdicts + hits through HBM (PCIe both ways); a stream
     // holds one staged batch at a time (the staging buffer is reused), so earlier ones complete first
     if (!S->pending.empty()) {
-        const int e0 = sync_pending(c, S);
-        if (e0 == GM_E_OVERFLOW)
-            return fail(c, GM_E_EARLIER, "an earlier batch of this stream completed void before the staged batch (" +
-                                         t_err + "); this batch was not enqueued");
+        const int e0 = forced_sync(c, S, "before the staged batch");
         if (e0) return e0;
         rp.slot = 0;
     }
@@ -3842,7 +3857,7 @@ extern "C" int gm_parse_requests(gm_ctx *c, const uint8_t *wire, const gm_wire_m
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_wtemp, tmp, S->d_wsize, S->d_wbase, (int)n + 1, s));
     // pass 2: the block map, the flat gather of nearly every slot (a lane per 16-byte chunk), the
-    // void batch's records, the full lists
+    // records of zero-size slots and of a void batch, the full lists
     const uint32_t lb = std::min<uint32_t>((n + 255) / 256, (uint32_t)c->cu_count * 8);
     k_wire_blk<<<lb, 256, 0, s>>>(S->d_wbase, n, S->d_wblk, nblk);
     HIPCHK(c, hipGetLastError());
@@ -3850,7 +3865,7 @@ extern "C" int gm_parse_requests(gm_ctx *c, const uint8_t *wire, const gm_wire_m
                                                            arena_len_dev, S->d_status + PARSE_STATUS_WORD, wsum, S->d_wblk,
                                                            fmask, S->d_wpieces);
     HIPCHK(c, hipGetLastError());
-    k_wire_void<<<lb, 256, 0, s>>>(msgs, n, S->d_wsize, S->d_wbase, reqs, arena_cap);
+    k_wire_void<<<lb, 256, 0, s>>>(msgs, n, S->d_wsize, S->d_wbase, reqs, arena_cap, wsum);
     HIPCHK(c, hipGetLastError());
     k_wire_emit_full<<<blocks, 64 * WIRE_WAVES, 0, s>>>(wire, msgs, n, S->d_wsize, S->d_wbase, reqs, arena, arena_cap,
                                                         S->d_wscr, wsum, fmask, S->d_wfull, per, fcnt);

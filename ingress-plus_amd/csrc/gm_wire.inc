@@ -1199,22 +1199,27 @@ __global__ __launch_bounds__(256) void k_wire_gather(const uint8_t *__restrict__
     }
 }
 
-// pass 2c: a void batch (the arena capacity exceeded: gm_sync reports GM_E_OVERFLOW) -- every
-// request whose slot lies past the capacity gets an empty invalid record inside it, so the
-// layout stays legal (a no-op when the slots fit)
+// pass 2c: the records no slot byte carries, a lane per request.  A zero-size slot inside the
+// capacity (an invalid request -- kind 2 -- without a connection address or a PROXY address: no
+// output chunk is its first, so k_wire_gather never reaches it) gets its empty record with pass
+// 1's status.  In a void batch (the arena capacity exceeded: gm_sync reports GM_E_OVERFLOW) every
+// request whose slot lies past the capacity gets an empty invalid record (500) inside it, so the
+// layout stays legal.
 __global__ void k_wire_void(const gm_wire_msg *__restrict__ msgs, uint32_t n, const uint64_t *__restrict__ sizes,
-                            const uint64_t *__restrict__ bases, gm_req *__restrict__ reqs, uint64_t cap) {
+                            const uint64_t *__restrict__ bases, gm_req *__restrict__ reqs, uint64_t cap,
+                            const WireSum *__restrict__ sums) {
     const uint64_t capa = cap & ~15ull;
-    if (bases[n] <= capa) return;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint64_t base = bases[i];
-        if (base + sizes[i] <= capa) continue;
+        const uint64_t base = bases[i], slot = sizes[i];
+        const bool fits = base + slot <= capa;
+        if (fits && slot != 0) continue;
         const gm_wire_msg &m = msgs[i];
+        const uint32_t st = fits ? sums[i].status : 500u;
         gm_req r = {};
         r.base = min(base, capa);
         r.port = m.port; r.remote_port = m.remote_port;
         r.flags = (m.flags & (GM_REQ_HTTPS | GM_REQ_HTTP2)) | GM_REQ_INVALID;
-        r.pad0[1] = 500 & 0xFF; r.pad0[2] = 500 >> 8;
+        r.pad0[1] = (uint8_t)st; r.pad0[2] = (uint8_t)(st >> 8);
         for (int k = 0; k < 16; k++) r.rid[k] = m.rid[k];
         reqs[i] = r;
     }

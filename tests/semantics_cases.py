@@ -323,8 +323,85 @@ def http_unknown_case():
     return b, cases
 
 
+def _edit_location(text, name, body):
+    """the rendered `location <name> { ... }` block: `body` (a string) replaces its directives, or
+    (a callable) maps them"""
+    head = "    location %s {\n" % name
+    i = text.index(head) + len(head)
+    j = text.index("    }\n", i)
+    return text[:i] + (body(text[i:j]) if callable(body) else body) + text[j:]
+
+
+ACCESS_ROUTES_REJECT = "allow / deny beside wallarm_mode"
+
+
+def access_routes_case():
+    """Server-level allow / deny beside wallarm_mode on VirtualServers with routes.  A
+    route location answers `return 418` in the rewrite phase and error_page takes the request to a
+    named location: the route location's own access phase never runs (nginx's phase order: rewrite
+    before access), so the named target decides --
+    - a `return` target answers in its rewrite phase: RETURN / REDIRECT for every client;
+    - a wallarm_mode off target runs the access module alone: PROXY for an allowed client, 403 for
+      a denied one;
+    - a target with the server's rules and wallarm_mode on defers (the two access-phase handlers'
+      order is not fixed);
+    - a route whose condition reads $remote_addr under a set_real_ip_from the engine cannot read (a
+      host name) defers before any target is known."""
+    ups = [{"name": f"u{k}", "service": f"svc{k}", "port": 80} for k in range(6)]
+    vs = {"metadata": {"name": "ar", "namespace": "default"},
+          "spec": {"host": "ar.example.com", "upstreams": ups,
+                   "routes": [{"path": "/m", "rules": {"conditions": [{"header": "x-t"}],
+                                                       "matches": [{"values": ["ret"], "upstream": "u1"},
+                                                                   {"values": ["off"], "upstream": "u2"}],
+                                                       "defaultUpstream": "u0"}},
+                              {"path": "/s", "splits": [{"weight": 30, "upstream": "u3"},
+                                                        {"weight": 30, "upstream": "u4"},
+                                                        {"weight": 40, "upstream": "u5"}]}]}}
+    unk = _rules_vs("aru.example.com", {"variable": "$remote_addr"}, ADDRS)
+    p = confgen.default_config_params()
+    files = confgen.virtual_server_files([vs, unk], base=p, pem_name="")
+    acl = "    wallarm_mode monitoring;\n    allow 10.0.0.0/8;\n    deny all;\n"
+    off = lambda d: "        wallarm_mode off;\n" + d   # noqa: E731
+    key = [k for k in files if k.endswith("_ar")][0]
+    t = files[key].replace("    server_tokens", acl + "    server_tokens", 1)
+    t = _edit_location(t, "@rules_0_match_0", "        return 204;\n")
+    t = _edit_location(t, "@rules_0_match_1", off)
+    t = _edit_location(t, "@splits_0_split_0", "        return 302 http://moved.example.com/;\n")
+    t = _edit_location(t, "@splits_0_split_1", off)
+    files[key] = t
+    key = [k for k in files if k.endswith("_aru")][0]
+    files[key] = files[key].replace("    server_tokens", "    set_real_ip_from unknown.example;\n" + acl +
+                                    "    server_tokens", 1)
+    assert files[key].count("wallarm_mode monitoring;") == 1 and t.count("wallarm_mode off;") == 2
+    b = blob.make_blob(confgen.render_main(p), files)
+    from oracle_py import murmur2
+    h, allowed, denied = "ar.example.com", "10.1.2.3", "192.168.1.1"
+    # a $request_id for each split_clients part: the first whose bound (30% / 60% / 100% of
+    # 0xffffffff) lies above murmur2 of the id's hex text
+    rid = {}
+    for k in range(64):
+        r = bytes([k] * 16)
+        hv = murmur2(r.hex().encode())
+        rid.setdefault(0 if hv < 3000 * 0xFFFFFFFF // 10000 else 1 if hv < 6000 * 0xFFFFFFFF // 10000 else 2, r)
+    cases = []
+    for ra in (allowed, denied):
+        m = {"host": h, "uri": "/m", "raddr": ra, "https": False}
+        s = {"host": h, "uri": "/s", "raddr": ra, "https": False}
+        cases += [
+            (dict(m, headers=[("X-T", "ret")]), RETURN),
+            (dict(s, rid=rid[0]), REDIRECT),
+            (dict(m, headers=[("X-T", "off")]), PROXY if ra == allowed else FORBIDDEN),
+            (dict(s, rid=rid[1]), PROXY if ra == allowed else FORBIDDEN),
+            (dict(m, headers=[("X-T", "other")]), UNSUPPORTED),     # the default target: WAF on, the server's rules
+            (dict(m), UNSUPPORTED),
+            (dict(s, rid=rid[2]), UNSUPPORTED),
+            ({"host": "aru.example.com", "uri": "/", "raddr": ra, "https": False}, UNSUPPORTED),
+        ]
+    return b, cases
+
+
 ROUTE_CASES = {"body_limit": body_limit_case, "vs_body": vs_body_case, "http_unknown": http_unknown_case,
-               "access": access_case}
+               "access": access_case, "access_routes": access_routes_case}
 # expected: the rules route's match index (0xFF default), or UNSUPPORTED for a deferred verdict
 MATCH_CASES = {"realip_xff": realip_xff_case, "realip_xrealip": realip_xrealip_case,
                "realip_header_port": realip_header_port_case, "realip_proxy_protocol": realip_proxy_protocol_case,

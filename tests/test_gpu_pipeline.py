@@ -527,6 +527,63 @@ def test_forced_sync_names_the_earlier_batch(torch_dev):
     e.close()
 
 
+@pytest.mark.parametrize("site", ["host_batch", "pending_max"])
+def test_forced_sync_passes_a_parse_overflow_through(torch_dev, site):
+    """GM_E_EARLIER means "an earlier BATCH is void".  A gm_parse_requests arena overflow
+    on the stream is no batch's: the sync a gm_match_batch forces (a GM_BATCH_HOST batch behind a
+    device batch; the 65th unsynced batch) answers GM_E_OVERFLOW as gm_sync would, gm_sync_batches
+    then lists every completed batch GM_OK, and their verdicts and counters are the oracle's."""
+    from gpumatch import wire
+    torch, dev = torch_dev
+    ss, b = workloads.c4_stress_generation()
+    r, a = records.gen_c4(64, ss, seed=workloads.C4_STRESS_POOL_SEED + 21, plant_rate=0.5, stress=True)
+    exp, eh = Oracle(b, 5).match(r, a)
+    assert len(eh) > 4
+    e = engine.Engine(0)
+    e.load(b, 5)
+    d_reqs, d_arena = _to_dev(torch, dev, r, a)
+    nb = 1 if site == "host_batch" else 64
+    outs = [torch.empty(len(r) * 32, dtype=torch.uint8, device=dev) for _ in range(nb + 1)]
+    hits = [torch.zeros(len(eh) + 1024, dtype=torch.int32, device=dev) for _ in range(nb + 1)]
+
+    def parse_into_a_third():
+        msgs, conn = wire.synthetic(3_000, seed=7)
+        W, M = wire.build(msgs, conn)
+        cap = (wire.arena_bound(M) // 3) & ~15
+        bufs = [torch.from_numpy(W).to(dev), torch.from_numpy(M.view(np.uint8).reshape(-1).copy()).to(dev),
+                torch.zeros(len(M) * 64, dtype=torch.uint8, device=dev),
+                torch.zeros(cap + 64, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)]
+        e.parse_ptr(bufs[0].data_ptr(), bufs[1].data_ptr(), len(M), bufs[2].data_ptr(), bufs[3].data_ptr(), cap,
+                    bufs[4].data_ptr(), 0)
+        return bufs
+
+    for i in range(nb):
+        e.match_ptr(d_reqs.data_ptr(), d_arena.data_ptr(), len(a), len(r), outs[i].data_ptr(), hits[i].data_ptr(),
+                    hits[i].numel(), 0)
+        if i == 0:
+            keep = parse_into_a_third()
+    with pytest.raises(engine.GmError) as ei:
+        if site == "host_batch":
+            ho, hh = np.zeros(len(r), dtype=records.VERDICT_DTYPE), np.zeros(len(eh) + 1024, dtype=np.uint32)
+            e.match_ptr(np.ascontiguousarray(r).ctypes.data, np.ascontiguousarray(a).ctypes.data, len(a), len(r),
+                        ho.ctypes.data, hh.ctypes.data, len(hh), 0, host=True)
+        else:
+            e.match_ptr(d_reqs.data_ptr(), d_arena.data_ptr(), len(a), len(r), outs[nb].data_ptr(),
+                        hits[nb].data_ptr(), hits[nb].numel(), 0)
+    assert ei.value.code == engine.GM_E_OVERFLOW, ei.value
+    assert "gm_parse_requests" in str(ei.value)
+    assert e.sync_batches(0) == [engine.GM_OK] * nb
+    one = None
+    for i in range(nb):
+        got = outs[i].cpu().numpy().view(records.VERDICT_DTYPE)
+        gh = hits[i][:len(eh)].cpu().numpy().view(np.uint32)
+        assert_verdicts_equal(got, exp, gh, eh, f"clean batch {i} before the parse overflow")
+        one = _one_batch_counters(e, got, gh)
+    assert np.array_equal(e.counters(), nb * one)   # the refused batch not counted
+    del keep
+    e.close()
+
+
 GM_ROUTE_HELD = 0x80
 
 

@@ -22,12 +22,12 @@ def env():
     return torch, torch.device("cuda", 0), engine.Engine(0)
 
 
-def _gpu_parse(torch, dev, e, W, M, stream=0, cap=None):
+def _gpu_parse(torch, dev, e, W, M, stream=0, cap=None, fill=0):
     n = len(M)
     cap = wire.arena_bound(M) if cap is None else cap
     d_w = torch.from_numpy(W).to(dev)
     d_m = torch.from_numpy(M.view(np.uint8).reshape(-1).copy()).to(dev)
-    d_r = torch.zeros(n * 64 + 16, dtype=torch.uint8, device=dev)
+    d_r = torch.full((n * 64 + 16,), fill, dtype=torch.uint8, device=dev)
     d_a = torch.full((cap + 64,), 0xAB, dtype=torch.uint8, device=dev)   # garbage: the parser zero-fills slack
     d_len = torch.zeros(1, dtype=torch.int64, device=dev)
     e.parse_ptr(d_w.data_ptr(), d_m.data_ptr(), n, d_r.data_ptr(), d_a.data_ptr(), cap, d_len.data_ptr(), stream)
@@ -88,6 +88,89 @@ def test_gpu_parse_matches_oracle(env):
         used[int(r["base"]):int(r["base"]) + tot] = True
     assert not ga[~used].any()
     assert (got["flags"] & records.REQ_INVALID).sum() > 100
+
+
+REC_FIELDS = ("flags", "pad0", "pad1", "uri_len", "args_len", "hdr_len", "body_len", "host_len", "method_len",
+              "ruri_len", "raddr_len", "port", "remote_port", "rid")
+
+
+def _check_records(got, ga, alen, exp, ea, msgs):
+    """the comparisons of test_gpu_parse_matches_oracle, and the bases"""
+    n = len(exp)
+    for f in REC_FIELDS:
+        bad = np.nonzero((got[f] != exp[f]).reshape(n, -1).any(axis=1))[0]
+        assert len(bad) == 0, (f, len(bad), int(bad[0]), msgs[int(bad[0])][:120], got[int(bad[0])], exp[int(bad[0])])
+    base = got["base"].astype(np.int64)
+    assert (base % 16 == 0).all() and (np.diff(base) >= 0).all() and (base <= alen).all()
+    assert np.array_equal(got["base"], exp["base"]) and alen == len(ea)
+    gf, ef = _fields(got, ga), _fields(exp, ea)
+    for f in records.WIRE_FIELDS:
+        assert gf[f] == ef[f], f
+    used = np.zeros(alen, bool)
+    for r in got:
+        tot = sum(records.field_len(r, f) for f in records.WIRE_FIELDS)
+        used[int(r["base"]):int(r["base"]) + tot] = True
+    assert not ga[~used].any()
+
+
+def test_zero_size_slots_get_records(env):
+    """an invalid request without a connection address and without a PROXY address takes
+    no arena byte, so no output chunk is its slot's first and the flat gather (a lane per 16-byte
+    chunk) never writes its record -- a lane per request does (k_wire_void).  tests/wire_cases.py's
+    batch (zero-size requests first, last, in a row, beside flat and full-list requests, on a block
+    edge of the output map; valid requests without an address) and a batch of nothing else (arena
+    length 0: the gather runs no iteration), into a record buffer pre-filled with 0xA5: every record
+    is the oracle's -- GM_REQ_INVALID with the status, the running base, the connection's ports
+    and request id."""
+    import wire_cases as WC
+    torch, dev, e = env
+    e.load(workloads.c2_blob(), 3)   # (a generation without a proxy_protocol port)
+    for msgs, conn in (WC.zero_slot_batch(), WC.only_zero_slots()):
+        W, M = wire.build(msgs, conn)
+        exp, ea = parse_requests(W, M)
+        zero = WC.slot_sizes(exp) == 0
+        assert zero[0] and zero[-1] and zero.sum() >= 300
+        if not zero.all():
+            k = WC.HEAD["k1024"]
+            assert zero[k] and exp["base"][k] % 1024 == 0 and exp["base"][k] > 0   # the block map's edge
+        d_w, d_m, d_r, d_a, d_len, cap = _gpu_parse(torch, dev, e, W, M, fill=0xA5)
+        e.sync(0)
+        n = len(M)
+        got = d_r[:n * 64].cpu().numpy().view(records.REQ_DTYPE)
+        alen = int(d_len.item())
+        assert (d_r[n * 64:].cpu().numpy() == 0xA5).all()
+        _check_records(got, d_a[:alen].cpu().numpy(), alen, exp, ea, msgs)
+        assert (got["flags"][zero] & records.REQ_INVALID).all()
+        st = got["pad0"][zero][:, 1].astype(int) | got["pad0"][zero][:, 2].astype(int) << 8
+        assert {400, 501, 505} <= set(st.tolist())
+        assert zero.all() == (alen == 0)
+
+
+def test_zero_size_slots_chain(env):
+    """The same batch through parse -> match on one stream: the requests without an arena byte come
+    out BAD_REQUEST with the parser's status (their record is read, not the caller's buffer)."""
+    import wire_cases as WC
+    torch, dev, e = env
+    blob = workloads.c2_blob()
+    msgs, conn = WC.zero_slot_batch()
+    W, M = wire.build(msgs, conn)
+    e.load(blob, 3)
+    d_w, d_m, d_r, d_a, d_len, cap = _gpu_parse(torch, dev, e, W, M, fill=0xA5)
+    n = len(M)
+    d_out = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+    d_h = torch.empty(4 * n + 1024, dtype=torch.int32, device=dev)
+    e.match_ptr(d_r.data_ptr(), d_a.data_ptr(), cap, n, d_out.data_ptr(), d_h.data_ptr(), d_h.numel(), 0,
+                arena_len_dev=d_len.data_ptr())
+    e.sync(0)
+    total = e.stats()["last_hits"]
+    got = d_out.cpu().numpy().view(records.VERDICT_DTYPE)
+    gh = d_h[:total].cpu().numpy().view(np.uint32)
+    reqs, arena = parse_requests(W, M)
+    exp, eh = Oracle(blob, 3).match(reqs, arena)
+    assert_verdicts_equal(got, exp, gh, eh, "zero-size slots chain")
+    zero = WC.slot_sizes(reqs) == 0
+    assert (got["action"][zero] == 5).all() and {400, 501, 505} <= set(got["status"][zero].tolist())
+    assert (got["action"][~zero] != 5).sum() > 500
 
 
 @pytest.mark.parametrize("cfg", ["c2", "c4"])

@@ -51,6 +51,33 @@ def test_default_deny_oracle_and_compile():
     assert st["n_rejected_other"] == len(got), (st["n_rejected_other"], got)
 
 
+def test_access_routes_oracle_and_compile():
+    """Routed VirtualServer locations under server-level allow / deny with wallarm_mode on (ADVICE
+    r6): the oracle's verdicts carry the route kind and index beside the answer, and the compile
+    defers no route location -- only the named targets that hold the rules beside wallarm_mode."""
+    b, cases = SC.access_routes_case()
+    v = _oracle(b, [c for c, _ in cases])
+    for (it, want), r in zip(cases, v):
+        assert r["action"] == want, (it, r)
+        if it["host"] != "ar.example.com":
+            assert r["route_kind"] == 3 and r["match_idx"] == 0xFF, (it, r)   # deferred before any target
+        elif it["uri"] == "/m":
+            x = dict(it.get("headers", [])).get("X-T")
+            assert r["route_kind"] == 3 and r["match_idx"] == {"ret": 0, "off": 1}.get(x, 0xFF), (it, r)
+            assert r["status"] == {SC.RETURN: 204, SC.FORBIDDEN: 403}.get(want, 0), (it, r)
+        else:
+            assert r["route_kind"] == 2 and r["split_bucket"] == {SC.REDIRECT: 0, SC.UNSUPPORTED: 2}.get(want, 1), (it, r)
+            assert r["status"] == {SC.REDIRECT: 302, SC.FORBIDDEN: 403}.get(want, 0), (it, r)
+    e = engine.Engine(compile_only=True)
+    e.load(b, 1)
+    got = [x for x in e.rejects() if SC.ACCESS_ROUTES_REJECT in x]
+    # the WAF-on targets (@rules_0_default, @splits_0_split_2; the second server's five proxy targets)
+    assert sorted(got) == sorted("location %s: %s" % (n, SC.ACCESS_ROUTES_REJECT) for n in
+                                 ["@rules_0_default", "@splits_0_split_2", "@rules_0_default"] +
+                                 ["@rules_0_match_%d" % k for k in range(4)]), e.rejects()
+    assert e.stats()["n_rejected_other"] == len(e.rejects())
+
+
 def test_http_unknown_counted_once():
     b, _ = SC.http_unknown_case()
     e = engine.Engine(compile_only=True)

@@ -58,6 +58,58 @@ def test_oracle_wire_known_answers():
     assert reqs[33]["hdr_len"] == len(b"Host: a\r\n") + 200 * len(b"X-H: 1\r\n")
 
 
+def test_oracle_request_without_address():
+    """gm_wire_msg.raddr_len 0 (include/gpumatch.h: "<= 40"): an invalid request without a
+    connection address takes no arena byte -- an empty record with the status, at the running base;
+    a valid one keeps its fields and an empty $remote_addr."""
+    import wire_cases as WC
+    C = {"https": False, "port": 80, "rid": bytes(range(16)), "remote_port": 4321}
+    msgs = [WC.BAD[2][0], b"GET /tea?x=1 HTTP/1.1\r\nHost: a\r\n\r\n", WC.BAD[3][0], WC.BAD[0][0], WC.UNKNOWN_METHOD]
+    W, M = wire.build(msgs, [dict(C, raddr="")] * 5)
+    assert (M["raddr_len"] == 0).all()
+    reqs, arena = parse_requests(W, M)
+    assert [_status(r) for r in reqs] == [505, 0, 501, 400, 0]
+    # /tea x=1 "Host: a\r\n" a GET /tea?x=1 = 4 + 3 + 9 + 1 + 3 + 8 = 28 bytes -> a 32-byte slot
+    # /pot "Host: cafe.example.com\r\n" cafe.example.com BREW /pot = 4 + 24 + 16 + 4 + 4 = 52 -> 64
+    assert reqs["base"].tolist() == [0, 0, 32, 32, 32] and len(arena) == 32 + 64
+    for i in (0, 2, 3):
+        r = reqs[i]
+        assert r["flags"] == records.REQ_INVALID and WC.slot_sizes(reqs[i:i + 1])[0] == 0
+        assert r["port"] == 80 and r["remote_port"] == 4321 and bytes(r["rid"]) == bytes(range(16))
+        assert not r["pad1"].any() and r["pad0"][0] == 0
+    assert records.field_bytes(reqs, arena, 1, "ruri") == b"/tea?x=1" and reqs[1]["raddr_len"] == 0
+    assert records.field_bytes(reqs, arena, 4, "method") == b"BREW"
+    assert records.field_bytes(reqs, arena, 4, "raddr") == b""
+
+
+def test_zero_slot_batch_places_its_cases():
+    """tests/wire_cases.py's batch, by the oracle's records: the zero-size requests stand where the
+    GPU test needs them (first, last, in a row, beside flat and full-list requests, on a multiple of
+    1024), with every status, and valid requests without an address among them."""
+    import wire_cases as WC
+    msgs, conn = WC.zero_slot_batch()
+    W, M = wire.build(msgs, conn)
+    reqs, arena = parse_requests(W, M)
+    size = WC.slot_sizes(reqs)
+    zero = np.nonzero(size == 0)[0]
+    H = WC.HEAD
+    want = [H["first"], H["between"], *H["row"], H["complex"] - 1, H["complex"] + 1, H["chunked"] - 1,
+            H["chunked"] + 1, H["k1024"], len(msgs) - 1]
+    assert set(want) <= set(zero.tolist()) and len(zero) > 300
+    for i in (H["between"] - 1, H["between"] + 1, H["complex"], H["chunked"], H["pad"], *H["valid_no_addr"]):
+        assert size[i] > 0 and _status(reqs[i]) == 0, i
+    assert reqs[H["complex"]]["uri_len"] < reqs[H["complex"]]["ruri_len"] - 4      # a rewritten path
+    assert reqs[H["chunked"]]["flags"] & records.REQ_CHUNKED and msgs[H["chunked"]].count(b"\r\n3\r\n") == 12
+    assert reqs[H["k1024"]]["base"] % 1024 == 0 and reqs[H["k1024"]]["base"] > 0
+    assert {400, 501, 505} <= {_status(reqs[i]) for i in zero}
+    assert ((M["raddr_len"] == 0) & (size > 0)).sum() > 50
+    assert (reqs["flags"][zero] & records.REQ_INVALID).all() and (reqs["base"][zero] <= len(arena)).all()
+    # the second batch: nothing but zero-size requests
+    W, M = wire.build(*WC.only_zero_slots())
+    reqs, arena = parse_requests(W, M)
+    assert len(arena) == 0 and not reqs["base"].any() and (reqs["flags"] & records.REQ_INVALID).all()
+
+
 def test_serialise_parse_round_trip():
     """records.gen_c2 requests -> HTTP/1.1 bytes -> the oracle's parser: the same fields."""
     reqs, arena = records.gen_c2(3000, seed=5)
