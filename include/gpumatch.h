@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 12u  /* 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
+#define GM_ABI_VERSION 13u  /* 13: gm_xml_bodies, GM_DEC_XML, gm_stats_t.last_xml (was reserved1); 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
                                7: GM_ACT_TOO_LARGE, GM_REQ_CHUNKED, gm_rejects, build flags; 6: n_rsl_reversed;
                                5: gm_update_upstream / gm_peers_migrate; 4: union-DFA stats */
 
@@ -53,7 +53,7 @@ extern "C" {
                                 batch that sync completed is void: any other outcome of the forced
                                 sync comes back as gm_sync reports it (GM_E_OVERFLOW for a
                                 gm_parse_requests / gm_upstream_uris / gm_inflate_bodies /
-                                gm_multipart_bodies capacity overflow: every batch is whole, and
+                                gm_multipart_bodies / gm_xml_bodies capacity overflow: every batch is whole, and
                                 this one was not enqueued either) */
 
 /* ---------------------------------------------------------------- gm_create flags */
@@ -271,7 +271,8 @@ typedef struct gm_stats_t {
     uint64_t csrc_hash;
     /* multipart bodies given a part view in the last batch (GM_DEC_MULTIPART) */
     uint32_t last_multipart;
-    uint32_t reserved1;
+    /* xml bodies given a character-data view in the last batch (GM_DEC_XML) */
+    uint32_t last_xml;
 } gm_stats_t;
 
 /* gm_stats_t.build_flags: measurement / test variants compiled into the library.  bench.py refuses
@@ -292,13 +293,17 @@ typedef struct gm_stats_t {
  *             Content-Type and its base64 runs are scanned after the raw body's parts
  *   multipart a multipart/form-data body's part view M (gm_multipart_bodies below: names, filenames
  *             and the part contents with base64 / quoted-printable undone); M, its JSON unescape if
- *             a part is JSON, and its base64 runs are scanned after everything above */
+ *             a part is JSON, and its base64 runs are scanned after everything above
+ *   xml       an XML body's character-data view X (gm_xml_bodies below: text, quoted attribute
+ *             values and CDATA sections, references replaced, comments removed); X and its base64
+ *             runs are scanned after everything above */
 #define GM_DEC_PERCENT 0x1u
 #define GM_DEC_URLENC  0x2u
 #define GM_DEC_JSON    0x4u
 #define GM_DEC_BASE64  0x8u
 #define GM_DEC_GZIP    0x10u
 #define GM_DEC_MULTIPART 0x20u
+#define GM_DEC_XML     0x40u
 
 typedef struct gm_ctx gm_ctx;
 
@@ -343,7 +348,7 @@ int         gm_sync(gm_ctx *ctx, void *stream);
  * gm_sync / gm_sync_batches on the stream, forced completions included, in enqueue order; it
  * returns that number of batches (entries past `cap` are not written), or a negative GM_E_* for an
  * error no batch status describes (HIP; gm_parse_requests / gm_upstream_uris / gm_inflate_bodies /
- * gm_multipart_bodies capacity, which gm_sync reports the same way, once: the sync that reports it
+ * gm_multipart_bodies / gm_xml_bodies capacity, which gm_sync reports the same way, once: the sync that reports it
  * clears it; the statuses are then kept for the next call).  gm_sync discards them. */
 int         gm_sync_batches(gm_ctx *ctx, void *stream, int32_t *status, size_t cap);
 
@@ -493,6 +498,44 @@ int         gm_inflate_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uin
 #define GM_MULTIPART_PARTS 64
 int         gm_multipart_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
                                 uint64_t *out_off, uint32_t *out_len, uint32_t *out_flags, void *stream);
+
+/* ---------------------------------------------------------------- xml request bodies
+ * (Wallarm's `xml` parser.)  The character-data view X of every XML body, a wave per
+ * body (gm_xml.inc states the same grammar beside the kernel).  Lenient on purpose: a WAF view, not a
+ * well-formedness check.
+ *  - Which bodies: body_len > 0 and the request's first Content-Type value contains "xml" (ASCII
+ *    case-insensitive), or the body, after an optional EF BB BF and any run of space, tab, CR and LF,
+ *    begins with "<?xml" (case-sensitive).  The body is read as sent: not inflated first, and a
+ *    multipart part is not read as XML.
+ *  - Scan: left to right from offset 0, starting in text.  At position p in text:
+ *      "<!--"       a comment, ends after the first "-->" that starts at q >= p + 2 ("<!-->" is whole);
+ *                   nothing is emitted, the text on either side joins.
+ *      "<![CDATA["  the bytes up to the first "]]>" at q >= p + 9 are emitted verbatim (no reference
+ *                   decoding), the scan continues at q + 3; a later "<![CDATA[" inside is content.
+ *      "<?"         ends after the first "?>" at q >= p + 1 ("<?>" is whole); nothing is emitted.
+ *      "<!" else    a declaration: '[' enters the subset, ']' leaves it, the first '>' outside the
+ *                   subset ends it; quotes are not considered; nothing is emitted.
+ *      '<' else     a tag: '\n' is emitted for the '<'.  Outside quotes '"' or ''' opens a quoted
+ *                   string that runs to the next same quote: its bytes are character data, its
+ *                   closing quote emits '\n'.  '>' outside quotes ends the tag; every other tag byte
+ *                   is dropped.
+ *      other bytes  character data.
+ *    A construct that the body's end cuts short just ends: what it emitted so far stands.
+ *  - Character data (text and quoted strings) is emitted as is, except references: at '&' one of
+ *    "&lt;" "&gt;" "&amp;" "&quot;" "&apos;" (case-sensitive), "&#" [0-9]{1,8} ";", "&#x" or "&#X"
+ *    [0-9A-Fa-f]{1,8} ";" is replaced by the byte or by the UTF-8 of v, 1 <= v <= 0x10FFFF outside
+ *    D800-DFFF; anything else leaves the '&' an ordinary byte.  The output is not decoded again:
+ *    "&amp;lt;" gives "&lt;".
+ *  - Out of scope: entity declarations of a DOCTYPE are not expanded; tag and attribute names and
+ *    unquoted attribute values are not emitted; encodings that are not ASCII-compatible are not
+ *    handled; quotes inside declarations are not considered.
+ *  - |X| <= body_len (proof in gm_xml.inc): request i's slot is body_len bytes.
+ * out_len[i] = |X| of request i's body at out[out_off[i]] (0 is a valid view); out_len[i] = GM_NONE: a
+ * body the selection rule does not take (or past out_cap: gm_sync then reports GM_E_OVERFLOW).
+ * out_cap >= in->arena_len always suffices.  Device pointers, asynchronous on `stream`, completed by
+ * gm_sync.  Needs no generation: the kernel gm_match_batch runs for a signature set that declares `xml`. */
+int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
+                          uint64_t *out_off, uint32_t *out_len, void *stream);
 
 /* ---------------------------------------------------------------- upstream peer selection
  * (the step after the path.)  The upstream blocks the templates render

@@ -133,6 +133,7 @@ uint32_t decoder_bit(const std::string &name) {
     if (name == "base64") return DEC_BASE64;
     if (name == "gzip") return DEC_GZIP;
     if (name == "multipart") return DEC_MULTIPART;
+    if (name == "xml") return DEC_XML;
     return 0;
 }
 

@@ -25,6 +25,9 @@
 //         names, filenames and the contents under their transfer encodings); after everything
 //         above: [M] [the JSON unescape of M if a part is JSON and it changes a byte] [each base64
 //         run of M, decoded]
+//   xml: an XML body's character-data view X (gm_xml.inc, run before these passes: text, quoted
+//         attribute values and CDATA sections, references replaced, comments removed); after
+//         everything above: [X] [each base64 run of X, decoded]
 // One lane per request (byte loops over $args and the body); two passes around an exclusive scan.
 
 constexpr uint32_t B64_MIN_RUN = 16;
@@ -190,9 +193,11 @@ __device__ uint32_t dec_body(const uint8_t *s, uint32_t n, uint32_t kind, uint32
 }
 
 // shadow record of request i: sizes (d = nullptr) or bytes at d; returns {args', body'} lengths.
-// P[0, pn): the body inflated (pn = GM_NONE: none); M[0, mn): its multipart view, mflags its flags
+// P[0, pn): the body inflated (pn = GM_NONE: none); M[0, mn): its multipart view, mflags its flags;
+// X[0, xn): its xml view
 __device__ uint2 dec_one(const uint8_t *A, const Rec &r, uint32_t mask, uint8_t *d, const uint8_t *P = nullptr,
-                         uint32_t pn = GM_NONE, const uint8_t *M = nullptr, uint32_t mn = GM_NONE, uint32_t mflags = 0) {
+                         uint32_t pn = GM_NONE, const uint8_t *M = nullptr, uint32_t mn = GM_NONE, uint32_t mflags = 0,
+                         const uint8_t *X = nullptr, uint32_t xn = GM_NONE) {
     const uint64_t args = r.base + r.uri_len, hdrs = args + r.args_len, body = hdrs + r.hdr_len;
     uint32_t a = 0, b = 0;
     if (mask & (DEC_PERCENT | DEC_URLENC)) {
@@ -216,12 +221,16 @@ __device__ uint2 dec_one(const uint8_t *A, const Rec &r, uint32_t mask, uint8_t 
         if (db) { for (uint32_t k = 0; k < mn; k++) db[b + k] = M[k]; db[b + mn] = '\n'; }
         b = dec_body(M, mn, (mflags & 1) ? 2u : 0u, mask, db, b + mn + 1);
     }
+    if (xn != GM_NONE) {
+        if (db) { for (uint32_t k = 0; k < xn; k++) db[b + k] = X[k]; db[b + xn] = '\n'; }
+        b = dec_body(X, xn, 0u, mask, db, b + xn + 1);
+    }
     return make_uint2(a, b);
 }
 
 __device__ __forceinline__ uint32_t dec_mask_of(const gm_verdict &v, const GTab &t) {
     if (!waf_active(v) || v.location_id >= t.n_locs) return 0;
-    return (t.loc_uri[v.location_id].flags >> LOCURI_DEC_SHIFT) & 63u;
+    return (t.loc_uri[v.location_id].flags >> LOCURI_DEC_SHIFT) & 127u;
 }
 
 __global__ void k_dec_size(const gm_req *__restrict__ reqs, const uint8_t *__restrict__ A, uint32_t n, GTab t,
@@ -229,15 +238,18 @@ __global__ void k_dec_size(const gm_req *__restrict__ reqs, const uint8_t *__res
                            const uint8_t *__restrict__ Z, const uint64_t *__restrict__ zoff,
                            const uint32_t *__restrict__ zlen, const uint8_t *__restrict__ MV,
                            const uint64_t *__restrict__ moff, const uint32_t *__restrict__ mlen,
-                           const uint32_t *__restrict__ mflg) {
+                           const uint32_t *__restrict__ mflg, const uint8_t *__restrict__ XV,
+                           const uint64_t *__restrict__ xoff, const uint32_t *__restrict__ xlen) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t mask = dec_mask_of(out[i], t);
         uint64_t sz = 0;
         if (mask) {
             const bool gz = Z && (mask & DEC_GZIP);
             const bool mp = MV && (mask & DEC_MULTIPART);
+            const bool xm = XV && (mask & DEC_XML);
             const uint2 ab = dec_one(A, load_rec(reqs + i), mask, nullptr, gz ? Z + zoff[i] : nullptr, gz ? zlen[i] : GM_NONE,
-                                     mp ? MV + moff[i] : nullptr, mp ? mlen[i] : GM_NONE, mp ? mflg[i] : 0u);
+                                     mp ? MV + moff[i] : nullptr, mp ? mlen[i] : GM_NONE, mp ? mflg[i] : 0u,
+                                     xm ? XV + xoff[i] : nullptr, xm ? xlen[i] : GM_NONE);
             sz = ((uint64_t)ab.x + ab.y + 15) & ~15ull;
         }
         sizes[i] = sz;
@@ -253,7 +265,9 @@ __global__ void k_dec_emit(const gm_req *__restrict__ reqs, const uint8_t *__res
                            uint32_t *__restrict__ status, const uint8_t *__restrict__ Z,
                            const uint64_t *__restrict__ zoff, const uint32_t *__restrict__ zlen,
                            const uint8_t *__restrict__ MV, const uint64_t *__restrict__ moff,
-                           const uint32_t *__restrict__ mlen, const uint32_t *__restrict__ mflg) {
+                           const uint32_t *__restrict__ mlen, const uint32_t *__restrict__ mflg,
+                           const uint8_t *__restrict__ XV, const uint64_t *__restrict__ xoff,
+                           const uint32_t *__restrict__ xlen) {
     const uint64_t total = base[n];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *len_dev = min(total, cap);
@@ -269,8 +283,10 @@ __global__ void k_dec_emit(const gm_req *__restrict__ reqs, const uint8_t *__res
             const Rec r = load_rec(reqs + i);
             const bool gz = Z && (mask & DEC_GZIP);
             const bool mp = MV && (mask & DEC_MULTIPART);
+            const bool xm = XV && (mask & DEC_XML);
             const uint2 ab = dec_one(A, r, mask, SA + b, gz ? Z + zoff[i] : nullptr, gz ? zlen[i] : GM_NONE,
-                                     mp ? MV + moff[i] : nullptr, mp ? mlen[i] : GM_NONE, mp ? mflg[i] : 0u);
+                                     mp ? MV + moff[i] : nullptr, mp ? mlen[i] : GM_NONE, mp ? mflg[i] : 0u,
+                                     xm ? XV + xoff[i] : nullptr, xm ? xlen[i] : GM_NONE);
             s.args_len = ab.x; s.body_len = ab.y;
             for (uint64_t k = b + ab.x + ab.y; k < b + sz; k++) SA[k] = 0;   // the slot's alignment tail
         }

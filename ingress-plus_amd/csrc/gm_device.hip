@@ -1685,6 +1685,7 @@ __global__ __launch_bounds__(ROUTE_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE
 #include "gm_decode.inc"
 #include "gm_inflate.inc"
 #include "gm_multipart.inc"
+#include "gm_xml.inc"
 
 }  // namespace
 
@@ -1789,6 +1790,15 @@ struct Scratch {
     uint32_t *d_mlen = nullptr; size_t cap_mlen = 0;
     uint32_t *d_mflg = nullptr; size_t cap_mflg = 0;
     uint8_t *d_mout = nullptr; size_t cap_mout = 0;
+    // xml bodies (gm_xml.inc): slot sizes, the bodies' list, control words, scan temp; the match
+    // path's slot offsets, lengths and views (only with DEC_XML)
+    uint64_t *d_xlim = nullptr; size_t cap_xlim = 0;
+    uint32_t *d_xlist = nullptr; size_t cap_xlist = 0;
+    uint32_t *d_xctl = nullptr; size_t cap_xctl = 0;
+    uint8_t *d_xtemp = nullptr; size_t cap_xtemp = 0;
+    uint64_t *d_xoff = nullptr; size_t cap_xoff = 0;
+    uint32_t *d_xlen = nullptr; size_t cap_xlen = 0;
+    uint8_t *d_xout = nullptr; size_t cap_xout = 0;
     uint2 *d_rq = nullptr; size_t cap_rq = 0;            // regex-location requests deferred to k_rloc
     int32_t *d_rql = nullptr; size_t cap_rql = 0;        // and k_rloc's locations
     uint4 *d_rqs = nullptr; size_t cap_rqs = 0;          // and each one's $uri span + server (k_rloc_multi)
@@ -1846,7 +1856,8 @@ struct Scratch {
                         (void *)d_hlist, (void *)d_hcnt, (void *)d_along, (void *)d_amlist, (void *)d_amcnt,
                         (void *)d_zlim, (void *)d_zlist, (void *)d_zctl, (void *)d_ztemp, (void *)d_zoff, (void *)d_zlen,
                         (void *)d_zout, (void *)d_mlim, (void *)d_mbnd, (void *)d_mlist, (void *)d_mctl, (void *)d_mtemp,
-                        (void *)d_moff, (void *)d_mlen, (void *)d_mflg, (void *)d_mout})
+                        (void *)d_moff, (void *)d_mlen, (void *)d_mflg, (void *)d_mout, (void *)d_xlim, (void *)d_xlist, (void *)d_xctl,
+                        (void *)d_xtemp, (void *)d_xoff, (void *)d_xlen, (void *)d_xout})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
         if (h_ovlog) (void)hipHostFree(h_ovlog);
@@ -1945,6 +1956,7 @@ struct gm_ctx {
     std::atomic<uint32_t> last_spill{0};      // pairs the last spill continuation emitted from the spill
     std::atomic<uint32_t> last_inflated{0};   // gzip bodies given a view in the last batch
     std::atomic<uint32_t> last_multipart{0};  // multipart bodies given a view in the last batch
+    std::atomic<uint32_t> last_xml{0};        // xml bodies given a view in the last batch
     std::shared_mutex gen_mu;                 // shared: enqueueing batches; exclusive: the swap
     Generation *gen = nullptr;
     uint64_t publish_seq = 0;                 // bumped under gen_mu (exclusive) by every publish
@@ -2283,7 +2295,7 @@ int gm_stats(gm_ctx *c, gm_stats_t *out) {
     out->last_spill = c->last_spill.load();
     out->last_inflated = c->last_inflated.load();
     out->last_multipart = c->last_multipart.load();
-    out->reserved1 = 0;
+    out->last_xml = c->last_xml.load();
     out->set_shift = c->set_shift;
     std::lock_guard<std::mutex> l2(c->last_mu);
     out->last_candidates = c->last_candidates;
@@ -2392,6 +2404,7 @@ struct WafIO {
     uint32_t nblk;
     uint32_t *infl_views = nullptr;   // the batch's count of inflated views (nullptr: a redo pass, not counted)
     uint32_t *mp_views = nullptr;     // and of multipart views
+    uint32_t *xml_views = nullptr;    // and of xml views
 };
 #ifndef GM_EXACT_BPC
 #define GM_EXACT_BPC 6
@@ -2527,6 +2540,35 @@ static int launch_multipart(gm_ctx *c, Scratch *S, const gm_req *reqs, const uin
     return GM_OK;
 }
 
+// The xml stage (gm_xml.inc), launched as the multipart stage: slot sizes (the bodies' lengths) and
+// the bodies' list, one exclusive scan, the persistent wave-per-body kernel.
+// verdicts + t, views, ov: as launch_inflate's.
+static int launch_xml(gm_ctx *c, Scratch *S, const gm_req *reqs, const uint8_t *A, uint64_t alen, const uint64_t *dlen,
+                      uint32_t n, const gm_verdict *verdicts, const GTab *t, uint8_t *out, uint64_t out_cap, uint64_t *off,
+                      uint32_t *len, uint32_t *views, uint32_t *ov) {
+    hipStream_t s = S->stream;
+    int e;
+    if ((e = grow(c, s, S->d_xlim, S->cap_xlim, (size_t)n + 1))) return e;
+    if ((e = grow(c, s, S->d_xlist, S->cap_xlist, (size_t)n))) return e;
+    if ((e = grow(c, s, S->d_xctl, S->cap_xctl, (size_t)XML_CTL_WORDS))) return e;
+    size_t tb = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, S->d_xlim, off, (int)n, s));
+    if ((e = grow(c, s, S->d_xtemp, S->cap_xtemp, tb))) return e;
+    k_xml_reset<<<1, 64, 0, s>>>(S->d_xctl);
+    HIPCHK(c, hipGetLastError());
+    const uint32_t sblocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, (uint32_t)c->cu_count * 8));
+    k_xml_size<<<sblocks, 256, 0, s>>>(reqs, A, alen, dlen, n, verdicts, t ? t->loc_uri : nullptr, t ? t->n_locs : 0u,
+                                       S->d_xlim, len, S->d_xlist, S->d_xctl);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_xtemp, tb, S->d_xlim, off, (int)n, s));
+    // 8 workgroups of 4 waves per CU: a wave's steps are dependent (the carried state), occupancy hides them
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + XML_WAVES - 1) / XML_WAVES, (uint32_t)c->cu_count * 8));
+    k_xml<<<blocks, XML_BLOCK, 0, s>>>(reqs, A, n, S->d_xlist, S->d_xctl, out, out_cap, off, len,
+                                       views ? views : S->d_xctl + 2, ov ? ov : S->d_xctl + 3);
+    HIPCHK(c, hipGetLastError());
+    return GM_OK;
+}
+
 static int launch_scan(gm_ctx *c, Scratch *S, const GTab &t, const WafCaps &k, const uint8_t *A, uint64_t alen,
                        const uint64_t *dlen) {
     hipStream_t s = S->stream;
@@ -2609,7 +2651,10 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
     // (with the multipart parser: a view M, |M| <= its body, adds M, its JSON transform and its base64 runs)
     const bool mpart = t.decoders & DEC_MULTIPART;
     const size_t mcap = mpart ? (size_t)io.alen + 16 : 0;
-    const size_t scap = 2 * (size_t)io.alen + 32 * (size_t)n + 4096 + 3 * zcap + 3 * mcap;   // a view <= 2x its zones
+    // (with the xml parser: a view X, |X| <= its body, adds X and its base64 runs)
+    const bool xml = t.decoders & DEC_XML;
+    const size_t xcap = xml ? (size_t)io.alen + 16 : 0;
+    const size_t scap = 2 * (size_t)io.alen + 32 * (size_t)n + 4096 + 3 * zcap + 3 * mcap + 2 * xcap;   // a view <= 2x its zones
     if (gzip) {
         if ((e = grow(c, s, S->d_zout, S->cap_zout, zcap))) return e;
         if ((e = grow(c, s, S->d_zoff, S->cap_zoff, (size_t)n))) return e;
@@ -2629,6 +2674,15 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
             return e;
     }
     const uint8_t *MV = mpart ? S->d_mout : nullptr;
+    if (xml) {
+        if ((e = grow(c, s, S->d_xout, S->cap_xout, xcap))) return e;
+        if ((e = grow(c, s, S->d_xoff, S->cap_xoff, (size_t)n))) return e;
+        if ((e = grow(c, s, S->d_xlen, S->cap_xlen, (size_t)n))) return e;
+        if ((e = launch_xml(c, S, io.reqs, io.A, io.alen, io.dlen, n, io.out, &t, S->d_xout, xcap, S->d_xoff, S->d_xlen,
+                            io.xml_views, nullptr)))
+            return e;
+    }
+    const uint8_t *XV = xml ? S->d_xout : nullptr;
     const uint32_t snblk = (uint32_t)((scap >> BLK_SHIFT) + 1);
     if ((e = grow(c, s, S->d_sreqs, S->cap_sreqs, (size_t)n))) return e;
     if ((e = grow(c, s, S->d_sarena, S->cap_sarena, scap))) return e;
@@ -2640,13 +2694,13 @@ static int waf_stages(gm_ctx *c, Scratch *S, const Generation *g, const WafCaps 
     if ((e = grow(c, s, S->d_stemp, S->cap_stemp, dtmp))) return e;
     const uint32_t dblocks = (n + 255) / 256;
     k_dec_size<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_ssize, Z, S->d_zoff, S->d_zlen, MV, S->d_moff, S->d_mlen,
-                                       S->d_mflg);
+                                       S->d_mflg, XV, S->d_xoff, S->d_xlen);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_stemp, dtmp, S->d_ssize, S->d_sbase, (int)n + 1, s));
     uint64_t *slen = S->d_sbase + n + 1;   // the shadow arena's length, on the device
     k_dec_emit<<<dblocks, 256, 0, s>>>(io.reqs, io.A, n, t, io.out, S->d_sbase, S->d_sreqs, S->d_sarena, scap,
                                        S->d_sblk, snblk, slen, S->d_status, Z, S->d_zoff, S->d_zlen, MV, S->d_moff,
-                                       S->d_mlen, S->d_mflg);
+                                       S->d_mlen, S->d_mflg, XV, S->d_xoff, S->d_xlen);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(S->d_status + 2, 0, 4, s));   // the job list restarts (pairs continue)
     k_status_pass<<<1, 64, 0, s>>>(S->d_status);   // the continuations restart too
@@ -2891,7 +2945,7 @@ static int run_batch(gm_ctx *c, Scratch *S, const Generation *g, const gm_req *r
     if (serial && (e = launch_route())) return e;
     if (mark(1)) return GM_E_HIP;
     const WafIO io{A, alen, dlen, reqs, n, out, S->d_blk2rec, nblk, S->d_status + INFL_VIEWS_WORD,
-                   S->d_status + MP_VIEWS_WORD};
+                   S->d_status + MP_VIEWS_WORD, S->d_status + XML_VIEWS_WORD};
     if ((e = waf_stages(c, S, g, k, io, dd, serial ? std::function<int()>() : std::function<int()>(launch_route), !serial,
                         mark))) return e;
     // ---- hit emission: offsets by an exclusive scan of the per-request counts (request order)
@@ -3145,6 +3199,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
         c->last_hits = S->h_status[4];
         c->last_inflated = S->h_status[INFL_VIEWS_WORD];
         c->last_multipart = S->h_status[MP_VIEWS_WORD];
+        c->last_xml = S->h_status[XML_VIEWS_WORD];
         if (S->ev_pending) {
             for (int k = 0; k < 4; k++) {
                 c->last_ms[k] = 0;
@@ -3157,6 +3212,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     }
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
     const uint32_t infl_ov = S->h_status[INFL_STATUS_WORD], mp_ov = S->h_status[MP_STATUS_WORD];
+    const uint32_t xml_ov = S->h_status[XML_STATUS_WORD];
     std::vector<Scratch::Replay> pend;
     pend.swap(S->pending);
     const bool last_in_place = S->last_is_batch;
@@ -3199,10 +3255,12 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     if (upuri_ov) HIPCHK(c, hipMemsetAsync(S->d_status + UPURI_STATUS_WORD, 0, 4, S->stream));
     if (infl_ov) HIPCHK(c, hipMemsetAsync(S->d_status + INFL_STATUS_WORD, 0, 4, S->stream));
     if (mp_ov) HIPCHK(c, hipMemsetAsync(S->d_status + MP_STATUS_WORD, 0, 4, S->stream));
+    if (xml_ov) HIPCHK(c, hipMemsetAsync(S->d_status + XML_STATUS_WORD, 0, 4, S->stream));
     if (parse_ov) return fail(c, GM_E_OVERFLOW, "gm_parse_requests: arena capacity exceeded");
     if (upuri_ov) return fail(c, GM_E_OVERFLOW, "gm_upstream_uris: output capacity exceeded");
     if (infl_ov) return fail(c, GM_E_OVERFLOW, "gm_inflate_bodies: output capacity exceeded");
     if (mp_ov) return fail(c, GM_E_OVERFLOW, "gm_multipart_bodies: output capacity exceeded");
+    if (xml_ov) return fail(c, GM_E_OVERFLOW, "gm_xml_bodies: output capacity exceeded");
     if (err & OV_HITS) return fail(c, GM_E_OVERFLOW, "hit_ids capacity exceeded (the batch's counters were not committed)");
     // candidate / survivor / pair / job overflows were completed on the device (k_waf_direct, the
     // set-based scatter and regex runs): the batch is whole, the buffers grow for speed
@@ -3314,7 +3372,8 @@ int gm_sync_batches(gm_ctx *c, void *stream, int32_t *status, size_t cap) {
     const int e = sync_pending(c, S);
     if (e && e != GM_E_OVERFLOW) return e;   // (a HIP error: the log stays for the next call)
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
-    if (e && (parse_ov || upuri_ov || S->h_status[INFL_STATUS_WORD] || S->h_status[MP_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
+    if (e && (parse_ov || upuri_ov || S->h_status[INFL_STATUS_WORD] || S->h_status[MP_STATUS_WORD] ||
+              S->h_status[XML_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
     const size_t n = S->sync_log.size();
     for (size_t i = 0; i < n && i < cap; i++) status[i] = S->sync_log[i];
     S->sync_log.clear();
@@ -4108,13 +4167,35 @@ extern "C" int gm_multipart_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, 
     return G.done(c);
 }
 
+// ---------------------------------------------------------------- xml request bodies (§8 f4)
+extern "C" int gm_xml_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                             uint32_t *out_len, void *stream) {
+    if (!c || !in) return fail(c, GM_E_INVAL, "null argument");
+    if (c->flags & GM_CREATE_COMPILE_ONLY) return fail(c, GM_E_NODEVICE, "compile-only context");
+    if (in->flags & GM_BATCH_HOST) return fail(c, GM_E_INVAL, "gm_xml_bodies takes device buffers");
+    const uint32_t n = in->n;
+    if (n && (!out_off || !out_len || !in->reqs || !in->arena || (!out && out_cap))) return fail(c, GM_E_INVAL, "null argument");
+    if ((uintptr_t)in->reqs & 15) return fail(c, GM_E_INVAL, "reqs must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t s = (hipStream_t)stream;
+    Scratch *S = scratch_for(c, s);
+    if (!S) return fail(c, GM_E_NOMEM, t_err);
+    DoneGuard G(S);
+    HIPCHK(c, hipMemsetAsync(S->d_status + XML_STATUS_WORD, 0, 4, s));
+    if (n == 0) return GM_OK;
+    if (int e = launch_xml(c, S, in->reqs, in->arena, in->arena_len, in->arena_len_dev, n, nullptr, nullptr, out, out_cap,
+                           out_off, out_len, nullptr, S->d_status + XML_STATUS_WORD))
+        return e;
+    return G.done(c);
+}
+
 // The request parsers location `loc` of the live generation runs (GM_DEC_* bits), < 0: no such location.
 extern "C" int gm_debug_loc_decoders(gm_ctx *c, uint32_t loc) {
     if (!c || !c->gen) return -1;
     const TabHeader &h = c->gen->hdr;
     if (loc >= h.n_locs) return -1;
     const DLocUri *lu = reinterpret_cast<const DLocUri *>(c->gen->host_image.data() + h.off_loc_uri);
-    return (int)((lu[loc].flags >> LOCURI_DEC_SHIFT) & 63u);
+    return (int)((lu[loc].flags >> LOCURI_DEC_SHIFT) & 127u);
 }
 
 // The measurement / tuning variants compiled in (gm_stats_t.build_flags): a bench line can show it

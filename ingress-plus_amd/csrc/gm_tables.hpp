@@ -148,10 +148,10 @@ struct DAccList { uint32_t first4, n4, first6, n6; };
 // The upstream request URI of a proxying location (§8 f1, nginx.org/rewrites: the URI part of
 // proxy_pass, annotations.go:347-361, version1/nginx.ingress.tmpl:194-196), indexed like DLoc.
 enum : uint32_t { LOCURI_REWRITE = 1, LOCURI_DEFER = 2 };
-// flags bits 8..13: the request parsers (Wallarm's, §8 f4) the location runs before the WAF
+// flags bits 8..14: the request parsers (Wallarm's, §8 f4) the location runs before the WAF
 // stages -- the signature set's "@decoders" minus wallarm_parser_disable
 constexpr uint32_t LOCURI_DEC_SHIFT = 8;
-enum : uint32_t { DEC_PERCENT = 1, DEC_URLENC = 2, DEC_JSON = 4, DEC_BASE64 = 8, DEC_GZIP = 16, DEC_MULTIPART = 32 };
+enum : uint32_t { DEC_PERCENT = 1, DEC_URLENC = 2, DEC_JSON = 4, DEC_BASE64 = 8, DEC_GZIP = 16, DEC_MULTIPART = 32, DEC_XML = 64 };
 struct DLocUri {
     uint32_t off, len;       // the URI part (bytes pool)
     uint32_t loc_len;        // the location's prefix length: $uri[loc_len:] follows the URI part

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GM_LIB") or os.path.join(os.path.dirname(HERE), "libgpumatch.so")
 
 GM_OK = 0
-GM_ABI_VERSION = 12   # include/gpumatch.h
+GM_ABI_VERSION = 13  # include/gpumatch.h
 GM_E_OVERFLOW = -4
 GM_E_STALE = -9
 GM_E_COMM = -7
@@ -70,7 +70,7 @@ class GmStats(ctypes.Structure):
                  ("last_redo", ctypes.c_uint32), ("last_spill", ctypes.c_uint32),
                  ("n_rsl_heads", ctypes.c_uint32), ("last_inflated", ctypes.c_uint32),
                  ("csrc_hash", ctypes.c_uint64), ("last_multipart", ctypes.c_uint32),
-                 ("reserved1", ctypes.c_uint32)])
+                 ("last_xml", ctypes.c_uint32)])
 
 
 class GmBatch(ctypes.Structure):
@@ -83,7 +83,7 @@ EXPORTS = ["gm_create", "gm_destroy", "gm_abi_version", "gm_load_generation", "g
            "gm_stats", "gm_last_error", "gm_normalize_uris", "gm_counters_global", "gm_parse_requests",
            "gm_peers_init", "gm_select_peers", "gm_release_peers", "gm_peer_address", "gm_upstream_uris",
            "gm_update_upstream", "gm_peers_migrate", "gm_rejects", "gm_build_hash", "gm_sync_batches",
-           "gm_inflate_bodies", "gm_multipart_bodies"]
+           "gm_inflate_bodies", "gm_multipart_bodies", "gm_xml_bodies"]
 
 # gm_peer_state (include/gpumatch.h)
 PEER_STATE_DTYPE = np.dtype([("conns", "<u4"), ("current_weight", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
@@ -140,7 +140,9 @@ def lib():
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.gm_multipart_bodies.argtypes = [ctypes.c_void_p, ctypes.POINTER(GmBatch), ctypes.c_void_p, ctypes.c_uint64,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.gm_rejects.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.gm_xml_bodies.argtypes = [ctypes.c_void_p, ctypes.POINTER(GmBatch), ctypes.c_void_p, ctypes.c_uint64,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.gm_rejects.argtypes =[ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         L.gm_build_hash.restype = ctypes.c_char_p
         L.gm_build_hash.argtypes = []
         L.gm_last_error.restype = ctypes.c_char_p
@@ -203,6 +205,7 @@ class Engine:
         d["last_spill"] = s.last_spill
         d["last_inflated"] = s.last_inflated
         d["last_multipart"] = s.last_multipart
+        d["last_xml"] = s.last_xml
         d["n_rsl_heads"] = s.n_rsl_heads
         d["set_shift"] = s.set_shift
         d["n_alw_members"] = s.n_alw_members
@@ -343,6 +346,34 @@ class Engine:
         out, off = d_out.cpu().numpy(), d_off.cpu().numpy()
         ln, fl = d_len.cpu().numpy().view(np.uint32), d_flg.cpu().numpy().view(np.uint32)
         return [None if ln[i] == GM_NONE else (out[off[i]:off[i] + ln[i]].tobytes(), int(fl[i])) for i in range(n)]
+
+    def xml_bodies_ptr(self, reqs_ptr, arena_ptr, arena_len, n, out_ptr, out_cap, off_ptr, len_ptr, stream=0):
+        """gm_xml_bodies on device pointers: the character-data view of every XML body (async)."""
+        b = GmBatch(reqs_ptr, arena_ptr, arena_len, n, 0, None)
+        self._chk(lib().gm_xml_bodies(self.h, ctypes.byref(b), out_ptr, out_cap, off_ptr, len_ptr, stream))
+
+    def xml_bodies(self, reqs: np.ndarray, arena: np.ndarray) -> list:
+        """Host numpy in (staged through device tensors), one entry per request out: the view bytes
+        of an XML body (the grammar of include/gpumatch.h; b"" is a valid view), None for a body
+        the selection rule does not take."""
+        import torch
+        n = len(reqs)
+        dev = torch.device("cuda", self.device)
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        arena = np.ascontiguousarray(arena, dtype=np.uint8) if len(arena) else np.zeros(16, np.uint8)
+        d_reqs = torch.from_numpy(reqs.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_arena = torch.from_numpy(arena.copy()).to(dev)
+        cap = len(arena) + 16   # |X| <= body_len
+        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        d_off = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        d_len = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.xml_bodies_ptr(d_reqs.data_ptr(), d_arena.data_ptr(), len(arena), n, d_out.data_ptr(), cap,
+                            d_off.data_ptr(), d_len.data_ptr(), 0)
+        self.sync(0)
+        out, off = d_out.cpu().numpy(), d_off.cpu().numpy()
+        ln = d_len.cpu().numpy().view(np.uint32)
+        return [None if ln[i] == GM_NONE else out[off[i]:off[i] + ln[i]].tobytes() for i in range(n)]
 
     def peer_address(self, peer: int):
         """(address, upstream id) of a global peer id."""

@@ -36,9 +36,10 @@ class Rule:
 
 class SigSet:
     """``decoders``: the request parsers (Wallarm's names: percent, urlenc, json_doc, base64, gzip,
-    multipart) whose decoded views of $args / the body the rules also scan ("@decoders" line,
+    multipart, xml) whose decoded views of $args / the body the rules also scan ("@decoders" line,
     gm_decode.inc; gzip: a body that is a gzip member, inflated on the device, gm_inflate.inc;
-    multipart: a multipart/form-data body's part view, gm_multipart.inc)."""
+    multipart: a multipart/form-data body's part view, gm_multipart.inc; xml: an XML body's
+    character-data view, gm_xml.inc)."""
 
     def __init__(self, rules, decoders=()):
         self.rules = list(rules)
