@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 13u  /* 13: gm_xml_bodies, GM_DEC_XML, gm_stats_t.last_xml (was reserved1); 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
+#define GM_ABI_VERSION 14u  /* 14: gm_auth_jwt, gm_auth_info, GM_ENTRY_JWK, gm_stats_t.n_auth_locations (appended); 13: gm_xml_bodies, GM_DEC_XML, gm_stats_t.last_xml (was reserved1); 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
                                7: GM_ACT_TOO_LARGE, GM_REQ_CHUNKED, gm_rejects, build flags; 6: n_rsl_reversed;
                                5: gm_update_upstream / gm_peers_migrate; 4: union-DFA stats */
 
@@ -196,6 +196,16 @@ enum { GM_WAF_OFF = 0, GM_WAF_MONITORING = 1, GM_WAF_SAFE_BLOCKING = 2, GM_WAF_B
 #define GM_ENTRY_CONFD    2u
 #define GM_ENTRY_SIGS     3u
 #define GM_ENTRY_SAMPLE   4u   /* optional: benign traffic sample bytes; tunes WAF key choice only */
+/* A JWT key file (NGINX Plus auth_jwt_key_file): `name` is the file's path exactly as the directive
+ * writes it (Configurator.GetFilenameForSecret, configurator.go:203), `data` the file's bytes -- the
+ * Secret's `jwk` field, a JWK set {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} ...]}.  With it
+ * the compiler accepts `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME | $http_NAME]` at server
+ * or location level iff the auth_jwt_key_file in effect names such an entry, the entry parses, all
+ * its keys are `kty: oct`, and an `error_page 401` beside it names a location of the template's
+ * shape (`internal; return 302 <url>;`).  In every other case the directive is rejected as before
+ * (a blob without the entry compiles as it always did).  Supplying the entry is the caller's promise
+ * to run gm_auth_jwt on the verdicts (below). */
+#define GM_ENTRY_JWK      5u
 
 typedef struct gm_stats_t {
     uint32_t gen;
@@ -273,6 +283,8 @@ typedef struct gm_stats_t {
     uint32_t last_multipart;
     /* xml bodies given a character-data view in the last batch (GM_DEC_XML) */
     uint32_t last_xml;
+    /* URI-selectable locations that carry an auth record (auth_jwt accepted: gm_auth_jwt, gm_auth_info) */
+    uint32_t n_auth_locations;
 } gm_stats_t;
 
 /* gm_stats_t.build_flags: measurement / test variants compiled into the library.  bench.py refuses
@@ -536,6 +548,65 @@ int         gm_multipart_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, u
  * gm_sync.  Needs no generation: the kernel gm_match_batch runs for a signature set that declares `xml`. */
 int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
                           uint64_t *out_off, uint32_t *out_len, void *stream);
+
+/* ---------------------------------------------------------------- auth_jwt (NGINX Plus)
+ * HS256 JWT verification for the locations `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME |
+ * $http_NAME]` protects (nginx-plus.ingress.tmpl:105-111,186-188,223-228; the nginx.com/jwt-key,
+ * jwt-realm, jwt-token and jwt-login-url annotations).  The key file is a GM_ENTRY_JWK entry of the
+ * blob; the compiler accepts the directive only then (see GM_ENTRY_JWK).  gm_match_batch does not
+ * run this pass: SUPPLYING THE JWK ENTRY IS THE CALLER'S PROMISE TO CALL gm_auth_jwt on the verdicts
+ * and to honour out_auth before it proxies -- without the entry such a location stays
+ * GM_ACT_UNSUPPORTED and goes to nginx whole.
+ * The grammar (gm_jwt.inc states the same beside the kernels):
+ *  - Which requests: the verdict's action is GM_ACT_PROXY or GM_ACT_BLOCK and its location carries an
+ *    auth record (its own auth_jwt, else its server's; `auth_jwt off` clears it; auth_jwt_key_file
+ *    and auth_jwt_leeway inherit the same way).  Everything else is answered before the access
+ *    phase, or is already denied: GM_AUTH_NONE.
+ *  - Token text: the source's value -- the first Authorization header's, which must begin with
+ *    "Bearer" (ASCII case-insensitive) and a space, further spaces skipped; or the named cookie's,
+ *    argument's or header's as nginx's variable reads it.  The token is its bytes up to the first
+ *    space or the value's end (none, or empty: NO_TOKEN).  It must be exactly three non-empty
+ *    segments of [A-Za-z0-9_-] split by two '.', with no padding; segment 3 is 43 characters (32
+ *    bytes); no segment is 4k + 1 characters long.  Anything else: MALFORMED.
+ *  - Header and payload decode as base64url to one JSON object each (whitespace around it allowed).
+ *    Top-level members only, the last of a repeated name winning: alg (a string: "HS256" goes on,
+ *    "none" is ALG_NONE, any other value DEFER; missing or not a string: MALFORMED), kid (a string,
+ *    optional), exp and nbf (optional; a JSON integer of 1..18 digits with an optional '-', or a
+ *    string of 1..18 decimal digits, as the reference's own minion token writes it; anything else
+ *    there: MALFORMED).  Nested values and strings are skipped with escapes honoured.  A member NAME
+ *    holding a backslash is MALFORMED (nginx would unescape it: the engine fails closed).
+ *  - Candidate keys: the set's keys whose kid equals the token's, if the token has a kid and any key
+ *    has that one; otherwise all keys (the first GM_JWT_KEYS of a set are read).
+ *  - Accept: some candidate key verifies -- HMAC-SHA-256 over the ASCII text segment1 "." segment2
+ *    as sent equals segment 3's bytes (else SIGNATURE) -- then exp + leeway > now (else EXPIRED) and
+ *    nbf <= now + leeway (else NOT_YET).  Claims are read only once the signature verified.
+ * out_auth[i] = code | reason << 8.  All pointers are device pointers (verdicts and in->reqs 16-byte
+ * aligned); `now` is Unix seconds; asynchronous on `stream`, completed by gm_sync, like
+ * gm_upstream_uris. */
+#define GM_JWT_KEYS 8
+enum {
+    GM_AUTH_NONE  = 0,   /* no auth record at the verdict's location, or not a PROXY / BLOCK verdict */
+    GM_AUTH_OK    = 1,   /* the token verifies                                                    */
+    GM_AUTH_DENY  = 2,   /* a 401 (gm_auth_info: the realm, the login location)                   */
+    GM_AUTH_DEFER = 3    /* nginx decides                                                         */
+};
+enum {
+    GM_AUTH_R_NO_TOKEN  = 1,   /* DENY: the source is absent, or holds no token                   */
+    GM_AUTH_R_MALFORMED = 2,   /* DENY: shape, base64url, JSON, alg missing, exp / nbf unreadable  */
+    GM_AUTH_R_ALG_NONE  = 3,   /* DENY: alg "none"                                                */
+    GM_AUTH_R_SIGNATURE = 4,   /* DENY: no candidate key verifies                                 */
+    GM_AUTH_R_EXPIRED   = 5,   /* DENY: exp + leeway <= now                                       */
+    GM_AUTH_R_NOT_YET   = 6,   /* DENY: nbf > now + leeway                                        */
+    GM_AUTH_R_ALG       = 7,   /* DEFER: alg is anything but HS256 (HS384, RS256, ES256, ...)     */
+    GM_AUTH_R_STALE     = 8    /* DEFER: the verdict is from another generation (or its record leaves the arena) */
+};
+int         gm_auth_jwt(gm_ctx *ctx, const gm_batch *in, const gm_verdict *verdicts, uint64_t now,
+                        uint32_t *out_auth, void *stream);
+/* Host: what a consumer answers GM_AUTH_DENY at `location_id` with -- the realm (WWW-Authenticate:
+ * Bearer realm="..."), written to `realm` (up to cap - 1 bytes, NUL-terminated), and the id of the
+ * named location `error_page 401` points at (jwt-login-url: `internal; return 302 <url>;`), GM_NONE
+ * if there is none.  Returns the realm's length; GM_E_INVAL: the location has no auth record. */
+int         gm_auth_info(gm_ctx *ctx, uint32_t location_id, char *realm, size_t cap, uint32_t *login_location);
 
 /* ---------------------------------------------------------------- upstream peer selection
  * (the step after the path.)  The upstream blocks the templates render

@@ -137,7 +137,197 @@ uint32_t decoder_bit(const std::string &name) {
     return 0;
 }
 
+// ---- auth_jwt (NGINX Plus): key files of the blob (GM_ENTRY_JWK) and the directives of a block
+struct JwkKey { std::string kid; bool has_kid = false; uint32_t inner[8], outer[8]; };
+struct JwkSet { bool ok = false; std::vector<JwkKey> keys; };   // ok: parses, every key `oct`
+struct AuthIR {
+    int state = -1;              // auth_jwt: -1 not given here, 0 `off`, 1 on
+    std::string realm, token;    // token: "" (Authorization: Bearer) or "token=$..."
+    bool has_file = false, has_leeway = false, leeway_bad = false, has_errpage = false;
+    std::string file;            // auth_jwt_key_file
+    uint32_t leeway = 0;         // auth_jwt_leeway, seconds
+    std::string login;           // error_page 401 <named location> ("" none)
+};
+
+static void sha256_block(uint32_t H[8], const uint8_t *b) {
+    auto ror = [](uint32_t x, int k) { return x >> k | x << (32 - k); };
+    uint32_t w[64], s[8];
+    for (int i = 0; i < 16; i++) w[i] = (uint32_t)b[4 * i] << 24 | b[4 * i + 1] << 16 | b[4 * i + 2] << 8 | b[4 * i + 3];
+    for (int i = 16; i < 64; i++)
+        w[i] = w[i - 16] + (ror(w[i - 15], 7) ^ ror(w[i - 15], 18) ^ (w[i - 15] >> 3)) + w[i - 7] +
+               (ror(w[i - 2], 17) ^ ror(w[i - 2], 19) ^ (w[i - 2] >> 10));
+    memcpy(s, H, sizeof s);
+    for (uint32_t i = 0; i < 64; i++) {
+        const uint32_t t1 = s[7] + (ror(s[4], 6) ^ ror(s[4], 11) ^ ror(s[4], 25)) + ((s[4] & s[5]) ^ (~s[4] & s[6])) + sha256_k(i) + w[i];
+        const uint32_t t2 = (ror(s[0], 2) ^ ror(s[0], 13) ^ ror(s[0], 22)) + ((s[0] & s[1]) ^ (s[0] & s[2]) ^ (s[1] & s[2]));
+        for (int k = 7; k > 0; k--) s[k] = s[k - 1];
+        s[4] += t1; s[0] = t1 + t2;
+    }
+    for (int i = 0; i < 8; i++) H[i] += s[i];
+}
+// HMAC-SHA-256's two midstates of a key (gm_tables.hpp DJwk)
+static void hmac_midstates(std::string key, uint32_t inner[8], uint32_t outer[8]) {
+    if (key.size() > 64) {   // RFC 2104: a key longer than the block is hashed first
+        uint32_t H[8];
+        memcpy(H, SHA256_IV, sizeof H);
+        std::string m = key;
+        const uint64_t bits = (uint64_t)key.size() * 8;
+        m += '\x80';
+        while (m.size() % 64 != 56) m += '\0';
+        for (int i = 7; i >= 0; i--) m += (char)(bits >> (8 * i));
+        for (size_t o = 0; o < m.size(); o += 64) sha256_block(H, (const uint8_t *)m.data() + o);
+        key.clear();
+        for (int i = 0; i < 8; i++) for (int k = 3; k >= 0; k--) key += (char)(H[i] >> (8 * k));
+    }
+    uint8_t blk[64];
+    for (int pass = 0; pass < 2; pass++) {
+        for (size_t i = 0; i < 64; i++) blk[i] = (uint8_t)((i < key.size() ? (uint8_t)key[i] : 0) ^ (pass ? 0x5c : 0x36));
+        uint32_t *H = pass ? outer : inner;
+        memcpy(H, SHA256_IV, sizeof SHA256_IV);
+        sha256_block(H, blk);
+    }
+}
+static bool b64url_decode(std::string t, std::string &out) {
+    while (!t.empty() && t.back() == '=') t.pop_back();
+    if (t.size() % 4 == 1) return false;
+    uint32_t acc = 0, bits = 0;
+    out.clear();
+    for (char ch : t) {
+        const uint32_t c = (uint8_t)ch;
+        uint32_t v;
+        if (c >= 'A' && c <= 'Z') v = c - 'A'; else if (c >= 'a' && c <= 'z') v = c - 'a' + 26;
+        else if (c >= '0' && c <= '9') v = c - '0' + 52; else if (c == '-') v = 62; else if (c == '_') v = 63;
+        else return false;
+        acc = acc << 6 | v; bits += 6;
+        if (bits >= 8) { bits -= 8; out += (char)(acc >> bits); }
+    }
+    return true;
+}
+// the little JSON a JWK set needs (no library): strings with their escapes, everything else skipped
+struct Json {
+    const char *p, *e;
+    void ws() { while (p < e && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) p++; }
+    bool lit(char c) { ws(); if (p < e && *p == c) { p++; return true; } return false; }
+    bool str(std::string &o) {
+        ws();
+        if (p >= e || *p != '"') return false;
+        for (p++, o.clear(); p < e && *p != '"';) {
+            char c = *p++;
+            if (c == '\\') {
+                if (p >= e) return false;
+                const char x = *p++;
+                if (x == 'u') {
+                    unsigned v = 0;
+                    if (e - p < 4) return false;
+                    for (int k = 0; k < 4; k++, p++) {
+                        if (!isxdigit((unsigned char)*p)) return false;
+                        v = v << 4 | (unsigned)(isdigit((unsigned char)*p) ? *p - '0' : (*p | 0x20) - 'a' + 10);
+                    }
+                    if (v < 0x80) o += (char)v;
+                    else if (v < 0x800) { o += (char)(0xC0 | v >> 6); o += (char)(0x80 | (v & 63)); }
+                    else { o += (char)(0xE0 | v >> 12); o += (char)(0x80 | (v >> 6 & 63)); o += (char)(0x80 | (v & 63)); }
+                    continue;
+                }
+                c = x == 'n' ? '\n' : x == 't' ? '\t' : x == 'r' ? '\r' : x == 'b' ? '\b' : x == 'f' ? '\f' : x;
+            }
+            o += c;
+        }
+        if (p >= e) return false;
+        p++;
+        return true;
+    }
+    bool skip(int depth = 0) {
+        ws();
+        if (p >= e || depth > 64) return false;
+        if (*p == '"') { std::string t; return str(t); }
+        if (*p == '{' || *p == '[') {
+            const bool obj = *p == '{';
+            const char close = obj ? '}' : ']';
+            p++;
+            if (lit(close)) return true;
+            do {
+                std::string k;
+                if (obj && (!str(k) || !lit(':'))) return false;
+                if (!skip(depth + 1)) return false;
+            } while (lit(','));
+            return lit(close);
+        }
+        const char *q = p;
+        while (p < e && !strchr(",}] \t\r\n", *p)) p++;
+        return p > q;
+    }
+};
+// {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} ...]}: the first JWT_KEYS_MAX keys are taken,
+// every key must be `oct` with a non-empty k
+static JwkSet parse_jwks(const char *data, size_t len) {
+    JwkSet S;
+    Json J{data, data + len};
+    bool have = false;
+    if (!J.lit('{')) return S;
+    if (!J.lit('}')) {
+        do {
+            std::string name;
+            if (!J.str(name) || !J.lit(':')) return S;
+            if (name != "keys") { if (!J.skip()) return S; continue; }
+            if (!J.lit('[')) return S;
+            have = true;
+            if (J.lit(']')) continue;
+            do {
+                std::string kty, kv, kid;
+                bool has_kid = false;
+                if (!J.lit('{')) return S;
+                if (!J.lit('}')) {
+                    do {
+                        std::string m;
+                        if (!J.str(m) || !J.lit(':')) return S;
+                        if (m == "kty") { if (!J.str(kty)) return S; }
+                        else if (m == "k") { if (!J.str(kv)) return S; }
+                        else if (m == "kid") { if (!J.str(kid)) return S; has_kid = true; }
+                        else if (!J.skip()) return S;
+                    } while (J.lit(','));
+                    if (!J.lit('}')) return S;
+                }
+                std::string key;
+                if (kty != "oct" || !b64url_decode(kv, key) || key.empty()) return S;
+                if (S.keys.size() < JWT_KEYS_MAX) {
+                    JwkKey K;
+                    K.kid = kid; K.has_kid = has_kid;
+                    hmac_midstates(key, K.inner, K.outer);
+                    S.keys.push_back(K);
+                }
+            } while (J.lit(','));
+            if (!J.lit(']')) return S;
+        } while (J.lit(','));
+        if (!J.lit('}')) return S;
+    }
+    J.ws();
+    S.ok = have && !S.keys.empty() && J.p == J.e;
+    return S;
+}
+// an nginx time value in seconds ("60s", "1m30s", "90")
+static bool parse_time_s(const std::string &t, uint32_t &out) {
+    uint64_t total = 0;
+    size_t i = 0;
+    if (t.empty()) return false;
+    while (i < t.size()) {
+        if (!isdigit((unsigned char)t[i])) return false;
+        uint64_t v = 0;
+        for (; i < t.size() && isdigit((unsigned char)t[i]); i++) if ((v = v * 10 + (uint64_t)(t[i] - '0')) > 0xFFFFFFFFull) return false;
+        uint64_t mul = 1;
+        if (i < t.size()) {
+            const char u = t[i++];
+            mul = u == 's' ? 1 : u == 'm' ? 60 : u == 'h' ? 3600 : u == 'd' ? 86400 : u == 'w' ? 604800 : u == 'M' ? 2592000 : u == 'y' ? 31536000 : 0;
+            if (!mul) return false;
+        }
+        if ((total += v * mul) > 0xFFFFFFFFull) return false;
+    }
+    out = (uint32_t)total;
+    return true;
+}
+
 struct Loc {
+    AuthIR auth;                 // the location's own auth directives, then (auth_on) the ones in effect
+    bool auth_on = false;        // auth_jwt in effect here and accepted: the location gets an auth record
     int id = 0, server = 0;
     LocKind kind = PFX;
     std::string path;
@@ -164,6 +354,9 @@ struct RealIpIR {
     bool bad = false;                // a value the engine does not model (a duplicate header)
 };
 struct Server {
+    AuthIR auth;                 // server-level auth directives
+    bool auth_ok = false;        // server-level auth_jwt accepted (else it defers the server as before)
+    std::set<std::string> logins;   // the login locations an accepted auth_jwt of this server names
     int id = 0, waf = GM_WAF_OFF;
     uint32_t parser_off = 0;     // server-level wallarm_parser_disable (DEC_* bits)
     std::string cmbs;            // server-level client_max_body_size ("" inherit)
@@ -208,6 +401,7 @@ struct Model {
     std::vector<std::pair<bool, std::string>> http_access;   // http-level allow / deny
     bool http_unknown = false;   // an http-level directive outside the known set: every server defers
     std::vector<std::string> reject_log;   // "context: directive" of every construct rejected
+    std::map<std::string, JwkSet> jwks;    // GM_ENTRY_JWK entries by key-file path
 };
 
 // ---- default-deny.  The directives the compile knows to leave a request's
@@ -269,7 +463,58 @@ struct Builder {
         M.reject_log.push_back(t);
     }
 
-    void location(Server &S, const Dir &d) {
+    // the auth directives a block gives itself
+    static AuthIR scan_auth(const std::vector<Dir> &body) {
+        AuthIR a;
+        for (const Dir &k : body) {
+            if (k.a.empty()) continue;
+            const std::string &n = k.a[0];
+            if (n == "auth_jwt" && k.a.size() == 2 && k.a[1] == "off") a.state = 0;
+            else if (n == "auth_jwt" && k.a.size() >= 2) {
+                a.state = 1; a.realm = k.a[1];
+                a.token = k.a.size() == 2 ? "" : k.a.size() == 3 ? k.a[2] : "?";
+            } else if (n == "auth_jwt_key_file" && k.a.size() == 2) { a.has_file = true; a.file = k.a[1]; }
+            else if (n == "auth_jwt_leeway" && k.a.size() == 2) { a.has_leeway = true; a.leeway_bad = !parse_time_s(k.a[1], a.leeway); }
+            else if (n == "error_page") { a.has_errpage = true; if (k.a.size() == 3 && k.a[1] == "401") a.login = k.a[2]; }
+        }
+        return a;
+    }
+    // nginx's inheritance: a block's own auth_jwt (`off` included), key file and leeway replace its
+    // parent's; error_page is inherited only by a block that has none of its own
+    static AuthIR merge_auth(const AuthIR &own, const AuthIR &up) {
+        AuthIR a = own;
+        if (own.state < 0) { a.state = up.state; a.realm = up.realm; a.token = up.token; }
+        if (!own.has_file) { a.has_file = up.has_file; a.file = up.file; }
+        if (!own.has_leeway) { a.has_leeway = up.has_leeway; a.leeway = up.leeway; a.leeway_bad = up.leeway_bad; }
+        if (!own.has_errpage) a.login = up.login;
+        return a;
+    }
+    // token=$cookie_NAME | $arg_NAME | $http_NAME (or none: the Authorization header)
+    static bool auth_token_src(const std::string &t, uint32_t &src, std::string &name) {
+        src = AUTH_SRC_BEARER; name.clear();
+        if (t.empty()) return true;
+        static const std::pair<const char *, uint32_t> pre[] = {{"token=$cookie_", SRC_COOKIE}, {"token=$arg_", SRC_ARG}, {"token=$http_", SRC_HTTP}};
+        for (auto &q : pre)
+            if (t.rfind(q.first, 0) == 0 && t.size() > strlen(q.first)) { src = q.second; name = lower(t.substr(strlen(q.first))); return true; }
+        return false;
+    }
+    // Whether the auth_jwt in effect is one the engine takes (include/gpumatch.h GM_ENTRY_JWK): its key
+    // file is a JWK entry that parsed to `oct` keys, and its login location, if any, is the
+    // template's `location @x { internal; return 302 <url>; }` (nginx-plus.ingress.tmpl:133-138)
+    bool auth_accept(const AuthIR &a, const Dir &srv) const {
+        uint32_t src; std::string nm;
+        if (a.state != 1 || !a.has_file || a.leeway_bad || !auth_token_src(a.token, src, nm)) return false;
+        auto it = M.jwks.find(a.file);
+        if (it == M.jwks.end() || !it->second.ok) return false;
+        if (a.login.empty()) return true;
+        for (const Dir &k : srv.body)
+            if (k.block && k.a.size() == 2 && k.a[0] == "location" && k.a[1] == a.login && a.login[0] == '@')
+                return k.body.size() == 2 && k.body[0].a.size() == 1 && k.body[0].a[0] == "internal" &&
+                       k.body[1].a.size() == 3 && k.body[1].a[0] == "return" && k.body[1].a[1] == "302";
+        return false;
+    }
+
+    void location(Server &S, const Dir &d, const Dir &srv) {
         Loc L;
         L.id = (int)M.locs.size(); L.server = S.id;
         if (d.a.size() == 3) {
@@ -282,6 +527,12 @@ struct Builder {
             L.kind = (!L.path.empty() && L.path[0] == '@') ? NAMED : PFX;
         }
         const std::string where = "location " + L.path;
+        const bool own_auth = scan_auth(d.body).state == 1;
+        L.auth = merge_auth(scan_auth(d.body), S.auth);
+        L.auth_on = L.kind != NAMED && auth_accept(L.auth, srv);
+        // auth in effect that the engine does not take, with no auth_jwt of the location's own to
+        // reject below and no server-level one deferring the server: the directive that broke it is rejected
+        const bool auth_broken = L.kind != NAMED && L.auth.state == 1 && !L.auth_on && !own_auth && S.auth_ok;
         for (const Dir &k : d.body) {
             if (k.a.empty()) continue;
             const std::string &n = k.a[0];
@@ -318,7 +569,12 @@ struct Builder {
                 L.nested = true;
                 reject(where, k);
             } else if (n == "auth_jwt" && k.a.size() == 2 && k.a[1] == "off") {
-            } else if (!neutral_directive(n, 2)) {
+            } else if (n == "auth_jwt" && L.auth_on) {
+            } else if (n == "error_page" && k.a.size() == 3 && k.a[1] == "401" && L.auth_on) {
+            } else if (n == "internal" && k.a.size() == 1 && S.logins.count(L.path)) {
+                // (the login location of an accepted auth_jwt; a named location is internal anyway)
+            } else if (!neutral_directive(n, 2) ||
+                       (auth_broken && (n == "auth_jwt_key_file" || n == "auth_jwt_leeway"))) {
                 L.unknown = true;
                 reject(where, k);
             }
@@ -345,6 +601,14 @@ struct Builder {
         Server S;
         S.id = (int)M.servers.size();
         S.waf = M.http_waf;
+        S.auth = scan_auth(d.body);
+        S.auth_ok = auth_accept(S.auth, d);
+        if (S.auth_ok && !S.auth.login.empty()) S.logins.insert(S.auth.login);
+        for (const Dir &k : d.body)
+            if (!M.jwks.empty() && k.block && k.a.size() >= 2 && k.a[0] == "location") {
+                const AuthIR a = merge_auth(scan_auth(k.body), S.auth);
+                if (!a.login.empty() && auth_accept(a, d)) S.logins.insert(a.login);
+            }
         for (const Dir &k : d.body) {
             if (k.a.size() == 2 && k.a[0] == "wallarm_mode") S.waf = waf_mode(k.a[1]);
             if (k.a.size() == 2 && k.a[0] == "wallarm_parser_disable") S.parser_off |= decoder_bit(k.a[1]);
@@ -405,7 +669,7 @@ struct Builder {
                 f.code = isdigit((unsigned char)k.a[1][0]) ? atoi(k.a[1].c_str()) : 302;
                 S.ifs.push_back(f);
             } else if (n == "location" && k.block) {
-                location(S, k);
+                location(S, k, d);
             } else if (n == "client_max_body_size" && k.a.size() == 2) {
                 S.cmbs = k.a[1];
             } else if ((n == "allow" || n == "deny") && k.a.size() == 2 && access_arg_ok(k.a[1])) {
@@ -414,6 +678,8 @@ struct Builder {
             } else if (n == "set" && k.a.size() >= 2 && k.a[1] == "$hsts_header_val") {
             } else if (n == "error_page" && k.a.size() >= 3 && k.a.back().rfind("@grpcerror", 0) == 0) {
             } else if (n == "auth_jwt" && k.a.size() == 2 && k.a[1] == "off") {
+            } else if (n == "auth_jwt" && S.auth_ok) {
+            } else if (n == "error_page" && k.a.size() == 3 && k.a[1] == "401" && S.auth_ok) {
             } else if (n == "rewrite" || !neutral_directive(n, 1)) {
                 // (a server-level rewrite, server snippets: not compiled either)
                 defer_here(k);
@@ -1504,6 +1770,7 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     std::vector<std::vector<Dir>> confd;
     const char *sig_text = nullptr; size_t sig_len = 0;
     KeyModel KM;
+    std::map<std::string, JwkSet> jwks;
     for (uint32_t e = 0; e < n; e++) {
         if (off + 12 > len) { R.code = GM_E_INVAL; R.err = "truncated blob"; return R; }
         uint32_t kind, nl, dl;
@@ -1514,6 +1781,7 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
         off += nl + dl;
         if (kind == GM_ENTRY_SIGS) { sig_text = data; sig_len = dl; continue; }
         if (kind == GM_ENTRY_SAMPLE) { KM.add_sample((const uint8_t *)data, dl); continue; }
+        if (kind == GM_ENTRY_JWK) { jwks[std::string(data - nl, nl)] = parse_jwks(data, dl); continue; }
         Tokenizer T(data, dl);
         std::vector<Dir> body;
         if (!parse_body(T, body, false)) {
@@ -1531,6 +1799,7 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     st.decoders = decoders;
 
     Model M;
+    M.jwks = std::move(jwks);
     Builder B(M, confd);
     if (have_main) {
         for (const Dir &d : main_body)
@@ -1712,6 +1981,9 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     std::vector<DLoc> dlocs(M.locs.size());
     for (DLoc &d : dlocs) d.access = GM_NONE;
     std::vector<DLocUri> dluri(M.locs.size());
+    std::vector<DAuth> dauth;                    // auth records: empty, or one per location
+    std::vector<DJwk> djwk;                      // the key sets in use, each once
+    std::map<std::string, uint32_t> jwk_first;   // key file -> its first DJwk
     std::vector<DNode> nodes;
     std::vector<std::pair<uint32_t, uint32_t>> edge_list;   // key, child
     std::map<std::pair<uint32_t, uint8_t>, uint32_t> edge_map;
@@ -1934,6 +2206,29 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
                 dl.kind != LK_IRL_RULES && dl.kind != LK_IRL_SPLIT) {
                 dl.kind = LK_UNSUPPORTED; st.n_rejected_other++;
                 R.rejects.push_back("location " + L.path + ": allow / deny beside wallarm_mode");
+            }
+
+            if (L.auth_on && !L.nested && !L.unknown) {   // the auth record (gm_tables.hpp DAuth)
+                if (dauth.empty()) { DAuth none{}; none.first_key = GM_NONE; dauth.assign(M.locs.size(), none); }
+                DAuth &da = dauth[lid];
+                auto ins = jwk_first.insert({L.auth.file, (uint32_t)djwk.size()});
+                const JwkSet &set = M.jwks[L.auth.file];
+                if (ins.second)
+                    for (const JwkKey &K : set.keys) {
+                        DJwk k{};
+                        memcpy(k.inner, K.inner, sizeof k.inner); memcpy(k.outer, K.outer, sizeof k.outer);
+                        k.kid_off = C.put_bytes(K.kid); k.kid_len = K.has_kid ? (uint32_t)K.kid.size() : GM_NONE;
+                        djwk.push_back(k);
+                    }
+                da.first_key = ins.first->second; da.n_keys = (uint32_t)set.keys.size();
+                std::string nm;
+                Builder::auth_token_src(L.auth.token, da.src, nm);
+                da.name_off = C.put_bytes(nm); da.name_len = (uint32_t)nm.size();
+                da.leeway = L.auth.leeway;
+                da.realm_off = C.put_bytes(L.auth.realm); da.realm_len = (uint32_t)L.auth.realm.size();
+                da.login_loc = GM_NONE;
+                for (int o : S.locs) if (!L.auth.login.empty() && M.locs[o].kind == NAMED && M.locs[o].path == L.auth.login) da.login_loc = (uint32_t)o;
+                st.n_auth_locations++;
             }
 
             if (L.kind == PFX || L.kind == NOREGEX || L.kind == EXACT) {
@@ -2598,6 +2893,8 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     h.off_realip = I.put(realips); h.off_cidrs = I.put(cidrs);
     h.n_acc_rules = (uint32_t)acc_rules.size(); h.n_acc_lists = (uint32_t)acc_lists.size();
     h.off_acc_rules = I.put(acc_rules); h.off_acc_lists = I.put(acc_lists);
+    h.n_auth = (uint32_t)dauth.size(); h.n_jwks = (uint32_t)djwk.size();
+    h.off_auth = I.put(dauth); h.off_jwks = I.put(djwk);
     h.n_rk_cap = rkcap; h.n_rk_ids = (uint32_t)rk_ids.size(); h.n_rk_ents_keys = (uint32_t)rk_lists.size();
     h.off_rk = I.put(rk); h.off_rk_ids = I.put(rk_ids); h.off_rk_ents = I.put(rk_ents); h.off_rk_bloom = I.put(rk_bloom);
     h.n_rk_ents_n = (uint32_t)rk_ents.size();

@@ -1686,6 +1686,7 @@ __global__ __launch_bounds__(ROUTE_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE
 #include "gm_inflate.inc"
 #include "gm_multipart.inc"
 #include "gm_xml.inc"
+#include "gm_jwt.inc"
 
 }  // namespace
 
@@ -1701,6 +1702,7 @@ struct Generation {
     size_t n_counters = 0;
     TabHeader hdr{};
     GTab tab{};
+    JwtTab jwt{};                                   // gm_auth_jwt's tables (gm_jwt.inc)
     gm_stats_t stats{};
     std::vector<uint8_t> host_image;   // kept for host-side introspection (gpumatch_debug.h)
     std::vector<std::string> peer_addrs;   // gm_peer_address
@@ -1799,6 +1801,12 @@ struct Scratch {
     uint64_t *d_xoff = nullptr; size_t cap_xoff = 0;
     uint32_t *d_xlen = nullptr; size_t cap_xlen = 0;
     uint8_t *d_xout = nullptr; size_t cap_xout = 0;
+    // gm_auth_jwt (gm_jwt.inc): per request a work item (two uint4) and the signature's eight
+    // words, the items' order by SHA block count, control words
+    uint4 *d_jit0 = nullptr, *d_jit1 = nullptr; size_t cap_jit0 = 0, cap_jit1 = 0;
+    uint32_t *d_jsig = nullptr; size_t cap_jsig = 0;
+    uint32_t *d_jord = nullptr; size_t cap_jord = 0;
+    uint32_t *d_jctl = nullptr; size_t cap_jctl = 0;
     uint2 *d_rq = nullptr; size_t cap_rq = 0;            // regex-location requests deferred to k_rloc
     int32_t *d_rql = nullptr; size_t cap_rql = 0;        // and k_rloc's locations
     uint4 *d_rqs = nullptr; size_t cap_rqs = 0;          // and each one's $uri span + server (k_rloc_multi)
@@ -1857,7 +1865,8 @@ struct Scratch {
                         (void *)d_zlim, (void *)d_zlist, (void *)d_zctl, (void *)d_ztemp, (void *)d_zoff, (void *)d_zlen,
                         (void *)d_zout, (void *)d_mlim, (void *)d_mbnd, (void *)d_mlist, (void *)d_mctl, (void *)d_mtemp,
                         (void *)d_moff, (void *)d_mlen, (void *)d_mflg, (void *)d_mout, (void *)d_xlim, (void *)d_xlist, (void *)d_xctl,
-                        (void *)d_xtemp, (void *)d_xoff, (void *)d_xlen, (void *)d_xout})
+                        (void *)d_xtemp, (void *)d_xoff, (void *)d_xlen, (void *)d_xout,
+                        (void *)d_jit0, (void *)d_jit1, (void *)d_jsig, (void *)d_jord, (void *)d_jctl})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
         if (h_ovlog) (void)hipHostFree(h_ovlog);
@@ -2206,6 +2215,8 @@ static int publish(gm_ctx *c, CompileResult &R, uint32_t gen, bool same_counters
         HIPCHK(c, hipMalloc((void **)&g->d_image, R.image.size()));
         HIPCHK(c, hipMemcpy(g->d_image, R.image.data(), R.image.size(), hipMemcpyHostToDevice));
         g->tab = make_gtab(g->hdr, g->d_image, gen);
+        g->jwt = JwtTab{g->hdr.n_auth ? reinterpret_cast<const DAuth *>(g->d_image + g->hdr.off_auth) : nullptr,
+                        reinterpret_cast<const DJwk *>(g->d_image + g->hdr.off_jwks), g->tab.bytes, g->hdr.n_locs, gen};
         HIPCHK(c, hipMalloc((void **)&g->d_gtab, sizeof(GTab)));
         g->tab.self = g->d_gtab;
         HIPCHK(c, hipMemcpy(g->d_gtab, &g->tab, sizeof(GTab), hipMemcpyHostToDevice));
@@ -4187,6 +4198,60 @@ extern "C" int gm_xml_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, uint64
                            out_off, out_len, nullptr, S->d_status + XML_STATUS_WORD))
         return e;
     return G.done(c);
+}
+
+// ---------------------------------------------------------------- auth_jwt (NGINX Plus)
+extern "C" int gm_auth_jwt(gm_ctx *c, const gm_batch *in, const gm_verdict *verdicts, uint64_t now, uint32_t *out_auth,
+                           void *stream) {
+    if (!c || !in) return fail(c, GM_E_INVAL, "null argument");
+    if (c->flags & GM_CREATE_COMPILE_ONLY) return fail(c, GM_E_NODEVICE, "compile-only context");
+    if (in->flags & GM_BATCH_HOST) return fail(c, GM_E_INVAL, "gm_auth_jwt takes device buffers");
+    const uint32_t n = in->n;
+    if (n && (!verdicts || !out_auth || !in->reqs || !in->arena)) return fail(c, GM_E_INVAL, "null argument");
+    if (((uintptr_t)verdicts & 15) || ((uintptr_t)in->reqs & 15)) return fail(c, GM_E_INVAL, "verdicts / reqs must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t s = (hipStream_t)stream;
+    Scratch *S = scratch_for(c, s);
+    if (!S) return fail(c, GM_E_NOMEM, t_err);
+    DoneGuard G(S);
+    std::shared_lock<std::shared_mutex> lk(c->gen_mu);
+    const Generation *g = c->gen;
+    if (!g) return fail(c, GM_E_NOGEN, "no generation loaded");
+    if (n == 0) return GM_OK;
+    int e;
+    if ((e = grow(c, s, S->d_jit0, S->cap_jit0, (size_t)n)) || (e = grow(c, s, S->d_jit1, S->cap_jit1, (size_t)n)) ||
+        (e = grow(c, s, S->d_jsig, S->cap_jsig, 8 * (size_t)n)) || (e = grow(c, s, S->d_jord, S->cap_jord, (size_t)n)) ||
+        (e = grow(c, s, S->d_jctl, S->cap_jctl, (size_t)JWT_CTL_WORDS)))
+        return e;
+    const uint32_t blocks = (n + 255) / 256, sblocks = std::min<uint32_t>(blocks, (uint32_t)c->cu_count * 8);
+    const long long now_s = (long long)std::min<uint64_t>(now, 1ull << 62);
+    k_jwt_reset<<<1, 256, 0, s>>>(S->d_jctl);
+    k_jwt_find<<<sblocks, 256, 0, s>>>(in->reqs, in->arena, in->arena_len, in->arena_len_dev, verdicts, n, g->jwt, S->d_jit0,
+                                       S->d_jit1, S->d_jsig, S->d_jctl, out_auth);
+    k_jwt_order<<<sblocks, 256, 0, s>>>(S->d_jit0, n, S->d_jctl, S->d_jord);
+    // (the work items are counted on the device: a block past them exits at once)
+    k_jwt_hmac<<<blocks, 256, 0, s>>>(in->arena, S->d_jctl, S->d_jord, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt.keys, n, out_auth);
+    k_jwt_claims<<<blocks, 256, 0, s>>>(in->arena, S->d_jctl, S->d_jord, S->d_jit0, S->d_jit1, n, now_s, out_auth);
+    HIPCHK(c, hipGetLastError());
+    return G.done(c);
+}
+
+extern "C" int gm_auth_info(gm_ctx *c, uint32_t location_id, char *realm, size_t cap, uint32_t *login_location) {
+    if (!c) return fail(c, GM_E_INVAL, "null ctx");
+    std::shared_lock<std::shared_mutex> lk(c->gen_mu);
+    const Generation *g = c->gen;
+    if (!g) return fail(c, GM_E_NOGEN, "no generation loaded");
+    const TabHeader &h = g->hdr;
+    if (location_id >= h.n_auth) return fail(c, GM_E_INVAL, "the location has no auth record");
+    const DAuth &a = reinterpret_cast<const DAuth *>(g->host_image.data() + h.off_auth)[location_id];
+    if (a.first_key == GM_NONE) return fail(c, GM_E_INVAL, "the location has no auth record");
+    if (realm && cap) {
+        const size_t k = std::min<size_t>(cap - 1, a.realm_len);
+        memcpy(realm, g->host_image.data() + h.off_bytes + a.realm_off, k);
+        realm[k] = 0;
+    }
+    if (login_location) *login_location = a.login_loc;
+    return (int)a.realm_len;
 }
 
 // The request parsers location `loc` of the live generation runs (GM_DEC_* bits), < 0: no such location.

@@ -158,6 +158,49 @@ struct DLocUri {
     uint32_t flags;          // 0: the request's own $request_uri goes upstream unchanged
 };
 
+// ---- auth_jwt (NGINX Plus; gm_jwt.inc) -------------------------------------------------
+// The auth record of a location (indexed like DLoc; the section is empty when no location has one):
+// the key set of the auth_jwt_key_file in effect, where the token is read from, auth_jwt_leeway,
+// and what a consumer answers a 401 with (gm_auth_info).  Kept out of GTab: only gm_auth_jwt's
+// kernels read it (JwtTab), and the route kernels' argument block stays as it was.
+constexpr uint32_t JWT_KEYS_MAX = 8;         // GM_JWT_KEYS: keys read from one JWK set
+enum : uint32_t { AUTH_SRC_BEARER = 0 };     // else SRC_HTTP / SRC_COOKIE / SRC_ARG
+struct DAuth {
+    uint32_t first_key;      // DJwk index of the set's first key; GM_NONE: the location has no auth record
+    uint32_t n_keys;         // 1 .. JWT_KEYS_MAX
+    uint32_t src;            // AUTH_SRC_BEARER (Authorization: Bearer), or SRC_* of token=$...
+    uint32_t name_off, name_len;   // the cookie / argument / header name (lowercase, '-' as '_'; bytes pool)
+    uint32_t leeway;         // auth_jwt_leeway, seconds
+    uint32_t realm_off, realm_len;
+    uint32_t login_loc;      // the `error_page 401` named location (jwt-login-url), GM_NONE: none
+    uint32_t pad[3];
+};
+// One `oct` key of a JWK set: HMAC-SHA-256's two midstates -- the SHA-256 state after the one block
+// K' ^ ipad and after K' ^ opad (K': the key zero-padded to 64 bytes, a longer key hashed first,
+// RFC 2104) -- so a token costs blocks + 2 compresses and the key itself never reaches the device.
+struct DJwk {
+    uint32_t inner[8], outer[8];
+    uint32_t kid_off, kid_len;     // the key's kid (bytes pool; kid_len 0: none)
+    uint32_t pad[2];
+};
+
+// SHA-256 (FIPS 180-4), shared by the host (the midstates) and k_jwt_hmac.  In a fully unrolled
+// round loop k is a literal, so the device reads no table.
+__host__ __device__ constexpr uint32_t sha256_k(uint32_t i) {
+    constexpr uint32_t K[64] = {
+        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
+        0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+        0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
+        0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+        0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+        0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+        0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
+        0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+    return K[i];
+}
+constexpr uint32_t SHA256_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
+                                   0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+
 // ---- request variables ---------------------------------------------------------------
 enum : uint8_t { SRC_HTTP = 1, SRC_COOKIE = 2, SRC_ARG = 3, SRC_VAR = 4 };
 enum : uint8_t { V_SCHEME = 1, V_HTTPS, V_HTTP2, V_METHOD, V_ARGS, V_URI, V_REQUEST_URI, V_REQUEST,
@@ -419,6 +462,8 @@ struct TabHeader {
     uint32_t n_wild, pad_wild;     // wildcard server names (both tables)
     uint32_t n_acc_rules, n_acc_lists;   // allow / deny rules and the lists locations point at
     uint64_t off_acc_rules, off_acc_lists;
+    uint32_t n_auth, n_jwks;             // DAuth records (0 or n_locs) and the DJwk keys of every set
+    uint64_t off_auth, off_jwks;
 };
 // The route's hot tables -- ports, the three name tables, servers, server ifs, small-location
 // lists, locations and the name strings -- are laid out first and contiguously in the image;

@@ -11,7 +11,7 @@ from __future__ import annotations
 import struct
 
 MAGIC = 0x31424D47
-ENTRY_MAIN, ENTRY_CONFD, ENTRY_SIGS, ENTRY_SAMPLE = 1, 2, 3, 4
+ENTRY_MAIN, ENTRY_CONFD, ENTRY_SIGS, ENTRY_SAMPLE, ENTRY_JWK = 1, 2, 3, 4, 5
 
 
 def _b(x):
@@ -19,10 +19,11 @@ def _b(x):
 
 
 def make_blob(main: str | bytes | None, confd: dict, sigs_text: str | bytes | None = None,
-              sample: bytes | None = None) -> bytes:
+              sample: bytes | None = None, jwks: dict | None = None) -> bytes:
     """``sample``: optional benign traffic bytes (GM_ENTRY_SAMPLE) -- the compiler uses them only to
     choose the WAF prefilter's key windows and hash multiplier; matching results never depend
-    on it."""
+    on it.  ``jwks``: JWT key files (GM_ENTRY_JWK), path as ``auth_jwt_key_file`` writes it -> the
+    file's bytes (a JWK set); supplying one promises that ``Engine.auth_jwt`` runs on the verdicts."""
     entries = []
     if main is not None:
         entries.append((ENTRY_MAIN, b"nginx.conf", _b(main)))
@@ -32,6 +33,8 @@ def make_blob(main: str | bytes | None, confd: dict, sigs_text: str | bytes | No
         entries.append((ENTRY_SIGS, b"signatures", _b(sigs_text)))
     if sample is not None:
         entries.append((ENTRY_SAMPLE, b"sample", _b(sample)))
+    for name in sorted(jwks or {}):
+        entries.append((ENTRY_JWK, _b(name), _b(jwks[name])))
     out = [struct.pack("<II", MAGIC, len(entries))]
     for kind, name, data in entries:
         out.append(struct.pack("<III", kind, len(name), len(data)))

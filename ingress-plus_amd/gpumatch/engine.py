@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GM_LIB") or os.path.join(os.path.dirname(HERE), "libgpumatch.so")
 
 GM_OK = 0
-GM_ABI_VERSION = 13  # include/gpumatch.h
+GM_ABI_VERSION = 14  # include/gpumatch.h
 GM_E_OVERFLOW = -4
 GM_E_STALE = -9
 GM_E_COMM = -7
@@ -70,7 +70,7 @@ class GmStats(ctypes.Structure):
                  ("last_redo", ctypes.c_uint32), ("last_spill", ctypes.c_uint32),
                  ("n_rsl_heads", ctypes.c_uint32), ("last_inflated", ctypes.c_uint32),
                  ("csrc_hash", ctypes.c_uint64), ("last_multipart", ctypes.c_uint32),
-                 ("last_xml", ctypes.c_uint32)])
+                 ("last_xml", ctypes.c_uint32), ("n_auth_locations", ctypes.c_uint32)])
 
 
 class GmBatch(ctypes.Structure):
@@ -83,7 +83,12 @@ EXPORTS = ["gm_create", "gm_destroy", "gm_abi_version", "gm_load_generation", "g
            "gm_stats", "gm_last_error", "gm_normalize_uris", "gm_counters_global", "gm_parse_requests",
            "gm_peers_init", "gm_select_peers", "gm_release_peers", "gm_peer_address", "gm_upstream_uris",
            "gm_update_upstream", "gm_peers_migrate", "gm_rejects", "gm_build_hash", "gm_sync_batches",
-           "gm_inflate_bodies", "gm_multipart_bodies", "gm_xml_bodies"]
+           "gm_inflate_bodies", "gm_multipart_bodies", "gm_xml_bodies", "gm_auth_jwt", "gm_auth_info"]
+
+# gm_auth_jwt: out_auth[i] = code | reason << 8 (include/gpumatch.h)
+GM_AUTH_NONE, GM_AUTH_OK, GM_AUTH_DENY, GM_AUTH_DEFER = 0, 1, 2, 3
+AUTH_REASON = {0: "", 1: "NO_TOKEN", 2: "MALFORMED", 3: "ALG_NONE", 4: "SIGNATURE", 5: "EXPIRED", 6: "NOT_YET",
+               7: "ALG", 8: "STALE"}
 
 # gm_peer_state (include/gpumatch.h)
 PEER_STATE_DTYPE = np.dtype([("conns", "<u4"), ("current_weight", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
@@ -142,6 +147,9 @@ def lib():
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.gm_xml_bodies.argtypes = [ctypes.c_void_p, ctypes.POINTER(GmBatch), ctypes.c_void_p, ctypes.c_uint64,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.gm_auth_jwt.argtypes = [ctypes.c_void_p, ctypes.POINTER(GmBatch), ctypes.c_void_p, ctypes.c_uint64,
+                                  ctypes.c_void_p, ctypes.c_void_p]
+        L.gm_auth_info.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
         L.gm_rejects.argtypes =[ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         L.gm_build_hash.restype = ctypes.c_char_p
         L.gm_build_hash.argtypes = []
@@ -206,6 +214,7 @@ class Engine:
         d["last_inflated"] = s.last_inflated
         d["last_multipart"] = s.last_multipart
         d["last_xml"] = s.last_xml
+        d["n_auth_locations"] = s.n_auth_locations
         d["n_rsl_heads"] = s.n_rsl_heads
         d["set_shift"] = s.set_shift
         d["n_alw_members"] = s.n_alw_members
@@ -374,6 +383,39 @@ class Engine:
         out, off = d_out.cpu().numpy(), d_off.cpu().numpy()
         ln = d_len.cpu().numpy().view(np.uint32)
         return [None if ln[i] == GM_NONE else out[off[i]:off[i] + ln[i]].tobytes() for i in range(n)]
+
+    def auth_jwt_ptr(self, reqs_ptr, arena_ptr, arena_len, n, verdicts_ptr, now, out_ptr, stream=0):
+        """gm_auth_jwt on device pointers: the auth_jwt outcome of every verdict (async)."""
+        b = GmBatch(reqs_ptr, arena_ptr, arena_len, n, 0, None)
+        self._chk(lib().gm_auth_jwt(self.h, ctypes.byref(b), verdicts_ptr, now, out_ptr, stream))
+
+    def auth_jwt(self, reqs: np.ndarray, arena: np.ndarray, verdicts: np.ndarray, now: int) -> np.ndarray:
+        """Host numpy in (staged through device tensors): out_auth of the batch's verdicts at Unix
+        time ``now`` -- GM_AUTH_* code | reason << 8 per request (the grammar of include/gpumatch.h)."""
+        import torch
+        n = len(reqs)
+        dev = torch.device("cuda", self.device)
+        reqs = np.ascontiguousarray(reqs, dtype=REQ_DTYPE)
+        verdicts = np.ascontiguousarray(verdicts, dtype=VERDICT_DTYPE)
+        arena = np.ascontiguousarray(arena, dtype=np.uint8) if len(arena) else np.zeros(16, np.uint8)
+        d_reqs = torch.from_numpy(reqs.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_ver = torch.from_numpy(verdicts.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_arena = torch.from_numpy(arena.copy()).to(dev)
+        d_out = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.auth_jwt_ptr(d_reqs.data_ptr(), d_arena.data_ptr(), len(arena), n, d_ver.data_ptr(), now,
+                          d_out.data_ptr(), 0)
+        self.sync(0)
+        return d_out.cpu().numpy().view(np.uint32)[:n]
+
+    def auth_info(self, location_id: int):
+        """gm_auth_info: (realm, login location id or GM_NONE) a DENY at the location is answered
+        with; None for a location without an auth record."""
+        buf = ctypes.create_string_buffer(1024)
+        login = ctypes.c_uint32(GM_NONE)
+        if lib().gm_auth_info(self.h, location_id, buf, 1024, ctypes.byref(login)) < 0:
+            return None
+        return buf.value.decode(), login.value
 
     def peer_address(self, peer: int):
         """(address, upstream id) of a global peer id."""
