@@ -198,10 +198,14 @@ enum { GM_WAF_OFF = 0, GM_WAF_MONITORING = 1, GM_WAF_SAFE_BLOCKING = 2, GM_WAF_B
 #define GM_ENTRY_SAMPLE   4u   /* optional: benign traffic sample bytes; tunes WAF key choice only */
 /* A JWT key file (NGINX Plus auth_jwt_key_file): `name` is the file's path exactly as the directive
  * writes it (Configurator.GetFilenameForSecret, configurator.go:203), `data` the file's bytes -- the
- * Secret's `jwk` field, a JWK set {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} ...]}.  With it
+ * Secret's `jwk` field, a JWK set {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} ...]}.  A set
+ * may mix `oct` keys and RSA public keys {"kty":"RSA","n":"<base64url>","e":"AQAB","kid":"..."}: e must
+ * decode to 65537 (leading zero bytes allowed) and n, leading zero bytes stripped, must be odd and
+ * exactly 2048, 3072 or 4096 bits long; every other member is skipped (a private JWK's d, p, q are
+ * never stored).  With it
  * the compiler accepts `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME | $http_NAME]` at server
  * or location level iff the auth_jwt_key_file in effect names such an entry, the entry parses, all
- * its keys are `kty: oct`, and an `error_page 401` beside it names a location of the template's
+ * its keys are such `oct` or RSA keys, and an `error_page 401` beside it names a location of the template's
  * shape (`internal; return 302 <url>;`).  In every other case the directive is rejected as before
  * (a blob without the entry compiles as it always did).  Supplying the entry is the caller's promise
  * to run gm_auth_jwt on the verdicts (below). */
@@ -550,7 +554,7 @@ int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_
                           uint64_t *out_off, uint32_t *out_len, void *stream);
 
 /* ---------------------------------------------------------------- auth_jwt (NGINX Plus)
- * HS256 JWT verification for the locations `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME |
+ * HS256 and RS256 JWT verification for the locations `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME |
  * $http_NAME]` protects (nginx-plus.ingress.tmpl:105-111,186-188,223-228; the nginx.com/jwt-key,
  * jwt-realm, jwt-token and jwt-login-url annotations).  The key file is a GM_ENTRY_JWK entry of the
  * blob; the compiler accepts the directive only then (see GM_ENTRY_JWK).  gm_match_batch does not
@@ -567,19 +571,29 @@ int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_
  *    argument's or header's as nginx's variable reads it.  The token is its bytes up to the first
  *    space or the value's end (none, or empty: NO_TOKEN).  It must be exactly three non-empty
  *    segments of [A-Za-z0-9_-] split by two '.', with no padding; segment 3 is 43 characters (32
- *    bytes); no segment is 4k + 1 characters long.  Anything else: MALFORMED.
+ *    bytes) -- or, where the location's set holds an RSA key, 342, 512 or 683; no segment is 4k + 1
+ *    characters long.  Anything else: MALFORMED.
  *  - Header and payload decode as base64url to one JSON object each (whitespace around it allowed).
  *    Top-level members only, the last of a repeated name winning: alg (a string: "HS256" goes on,
- *    "none" is ALG_NONE, any other value DEFER; missing or not a string: MALFORMED), kid (a string,
+ *    and "RS256" where the set holds an RSA key; "none" is ALG_NONE, any other value DEFER; missing
+ *    or not a string: MALFORMED), kid (a string,
  *    optional), exp and nbf (optional; a JSON integer of 1..18 digits with an optional '-', or a
  *    string of 1..18 decimal digits, as the reference's own minion token writes it; anything else
  *    there: MALFORMED).  Nested values and strings are skipped with escapes honoured.  A member NAME
  *    holding a backslash is MALFORMED (nginx would unescape it: the engine fails closed).
- *  - Candidate keys: the set's keys whose kid equals the token's, if the token has a kid and any key
- *    has that one; otherwise all keys (the first GM_JWT_KEYS of a set are read).
- *  - Accept: some candidate key verifies -- HMAC-SHA-256 over the ASCII text segment1 "." segment2
- *    as sent equals segment 3's bytes (else SIGNATURE) -- then exp + leeway > now (else EXPIRED) and
- *    nbf <= now + leeway (else NOT_YET).  Claims are read only once the signature verified.
+ *  - Candidate keys: the set's keys of the alg's kind (`oct` for HS256, RSA for RS256: an RSA key is
+ *    never an HMAC key) whose kid equals the token's, if the token has a kid and any key of the kind
+ *    has that one; otherwise all keys of the kind (the first GM_JWT_KEYS of a set are read, of both
+ *    kinds together).  No key of the kind: SIGNATURE.
+ *  - Accept: some candidate key verifies (else SIGNATURE).  HS256: segment 3 is 43 characters (else
+ *    MALFORMED) and HMAC-SHA-256 over the ASCII text segment1 "." segment2 as sent equals its bytes.
+ *    RS256, a key whose modulus n is k bytes: segment 3 is ceil(4k / 3) characters, its first 8k
+ *    bits as a big-endian integer s are < n (surplus bits ignored, as for HS256), and s^65537 mod n
+ *    equals, over all k bytes, the EMSA-PKCS1-v1_5 encoding 00 01 FF..FF 00 | 30 31 30 0d 06 09 60 86
+ *    48 01 65 03 04 02 01 05 00 04 20 | SHA-256(segment1 "." segment2); nothing inside the padding is
+ *    parsed.  Then exp + leeway > now (else EXPIRED) and nbf <= now + leeway (else NOT_YET).  Claims
+ *    are read only once the signature verified.
+ *    A location whose set holds no RSA key answers every input exactly as before RS256 was known.
  * out_auth[i] = code | reason << 8.  All pointers are device pointers (verdicts and in->reqs 16-byte
  * aligned); `now` is Unix seconds; asynchronous on `stream`, completed by gm_sync, like
  * gm_upstream_uris. */
@@ -597,7 +611,7 @@ enum {
     GM_AUTH_R_SIGNATURE = 4,   /* DENY: no candidate key verifies                                 */
     GM_AUTH_R_EXPIRED   = 5,   /* DENY: exp + leeway <= now                                       */
     GM_AUTH_R_NOT_YET   = 6,   /* DENY: nbf > now + leeway                                        */
-    GM_AUTH_R_ALG       = 7,   /* DEFER: alg is anything but HS256 (HS384, RS256, ES256, ...)     */
+    GM_AUTH_R_ALG       = 7,   /* DEFER: alg is anything but HS256, or RS256 where the set has an RSA key */
     GM_AUTH_R_STALE     = 8    /* DEFER: the verdict is from another generation (or its record leaves the arena) */
 };
 int         gm_auth_jwt(gm_ctx *ctx, const gm_batch *in, const gm_verdict *verdicts, uint64_t now,

@@ -138,8 +138,11 @@ uint32_t decoder_bit(const std::string &name) {
 }
 
 // ---- auth_jwt (NGINX Plus): key files of the blob (GM_ENTRY_JWK) and the directives of a block
-struct JwkKey { std::string kid; bool has_kid = false; uint32_t inner[8], outer[8]; };
-struct JwkSet { bool ok = false; std::vector<JwkKey> keys; };   // ok: parses, every key `oct`
+struct JwkKey {
+    std::string kid; bool has_kid = false; uint32_t inner[8], outer[8];
+    std::vector<uint32_t> n, rr;   // an RSA key (n not empty): gm_tables.hpp DJwk; n0inv in inner[0]
+};
+struct JwkSet { bool ok = false; std::vector<JwkKey> keys; };   // ok: parses, every key `oct` or an RSA key the engine takes
 struct AuthIR {
     int state = -1;              // auth_jwt: -1 not given here, 0 `off`, 1 on
     std::string realm, token;    // token: "" (Authorization: Bearer) or "token=$..."
@@ -257,8 +260,42 @@ struct Json {
         return p > q;
     }
 };
-// {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} ...]}: the first JWT_KEYS_MAX keys are taken,
-// every key must be `oct` with a non-empty k
+// An RSA public key the engine takes: e = 65537 (leading zero bytes allowed), n -- leading zero bytes
+// stripped -- odd and exactly 2048, 3072 or 4096 bits.  Fills the limbs of n and of RR = 2^(64 K) mod n,
+// and inner[0] = -1/n mod 2^32 (gm_tables.hpp DJwk).
+static bool rsa_key(const std::string &nb, const std::string &eb, JwkKey &K) {
+    size_t z = 0;
+    while (z < eb.size() && eb[z] == 0) z++;
+    if (eb.size() - z != 3 || eb[z] != 1 || eb[z + 1] != 0 || eb[z + 2] != 1) return false;
+    for (z = 0; z < nb.size() && nb[z] == 0;) z++;
+    const size_t k = nb.size() - z;
+    if ((k != 256 && k != 384 && k != 512) || !((uint8_t)nb[z] & 0x80) || !((uint8_t)nb.back() & 1)) return false;
+    const size_t L = k / 4;
+    K.n.assign(L, 0);
+    for (size_t i = 0; i < k; i++) K.n[i / 4] |= (uint32_t)(uint8_t)nb[nb.size() - 1 - i] << (8 * (i % 4));
+    // RR: 1 doubled 64 K times mod n by shift and subtract (x < n < 2^(32 K): 2 x has at most one bit more)
+    std::vector<uint32_t> x(L, 0);
+    x[0] = 1;
+    for (size_t s = 0; s < 64 * L; s++) {
+        uint32_t top = 0;
+        for (size_t j = 0; j < L; j++) { const uint32_t v = x[j]; x[j] = v << 1 | top; top = v >> 31; }
+        bool ge = true;
+        if (!top) for (size_t j = L; j-- > 0;) if (x[j] != K.n[j]) { ge = x[j] > K.n[j]; break; }
+        if (ge) {
+            uint64_t bw = 0;
+            for (size_t j = 0; j < L; j++) { const uint64_t d = (uint64_t)x[j] - K.n[j] - bw; x[j] = (uint32_t)d; bw = d >> 63; }
+        }
+    }
+    K.rr = x;
+    uint32_t inv = 1;   // Newton: each step doubles the correct low bits of 1/n, 1 -> 32
+    for (int i = 0; i < 5; i++) inv *= 2u - K.n[0] * inv;
+    memset(K.inner, 0, sizeof K.inner); memset(K.outer, 0, sizeof K.outer);
+    K.inner[0] = 0u - inv;
+    return true;
+}
+// {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} | {"kty":"RSA","n":"...","e":"AQAB","kid":"..."} ...]}:
+// the first JWT_KEYS_MAX keys are taken; every key must be `oct` with a non-empty k, or an RSA key
+// rsa_key takes (any further member -- a private JWK's d, p, q -- is skipped and never stored)
 static JwkSet parse_jwks(const char *data, size_t len) {
     JwkSet S;
     Json J{data, data + len};
@@ -273,7 +310,7 @@ static JwkSet parse_jwks(const char *data, size_t len) {
             have = true;
             if (J.lit(']')) continue;
             do {
-                std::string kty, kv, kid;
+                std::string kty, kv, kid, kn, ke;
                 bool has_kid = false;
                 if (!J.lit('{')) return S;
                 if (!J.lit('}')) {
@@ -283,18 +320,21 @@ static JwkSet parse_jwks(const char *data, size_t len) {
                         if (m == "kty") { if (!J.str(kty)) return S; }
                         else if (m == "k") { if (!J.str(kv)) return S; }
                         else if (m == "kid") { if (!J.str(kid)) return S; has_kid = true; }
+                        else if ((m == "n" || m == "e") && (J.ws(), J.p < J.e && *J.p == '"')) { if (!J.str(m == "n" ? kn : ke)) return S; }
                         else if (!J.skip()) return S;
                     } while (J.lit(','));
                     if (!J.lit('}')) return S;
                 }
-                std::string key;
-                if (kty != "oct" || !b64url_decode(kv, key) || key.empty()) return S;
-                if (S.keys.size() < JWT_KEYS_MAX) {
-                    JwkKey K;
-                    K.kid = kid; K.has_kid = has_kid;
+                std::string key, nb, eb;
+                JwkKey K;
+                K.kid = kid; K.has_kid = has_kid;
+                if (kty == "RSA") {
+                    if (!b64url_decode(kn, nb) || !b64url_decode(ke, eb) || !rsa_key(nb, eb, K)) return S;
+                } else {
+                    if (kty != "oct" || !b64url_decode(kv, key) || key.empty()) return S;
                     hmac_midstates(key, K.inner, K.outer);
-                    S.keys.push_back(K);
                 }
+                if (S.keys.size() < JWT_KEYS_MAX) S.keys.push_back(K);
             } while (J.lit(','));
             if (!J.lit(']')) return S;
         } while (J.lit(','));
@@ -1983,6 +2023,7 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     std::vector<DLocUri> dluri(M.locs.size());
     std::vector<DAuth> dauth;                    // auth records: empty, or one per location
     std::vector<DJwk> djwk;                      // the key sets in use, each once
+    std::vector<uint32_t> jwk_limbs;             // their RSA keys' n and RR (DJwk.limb_off)
     std::map<std::string, uint32_t> jwk_first;   // key file -> its first DJwk
     std::vector<DNode> nodes;
     std::vector<std::pair<uint32_t, uint32_t>> edge_list;   // key, child
@@ -2218,9 +2259,15 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
                         DJwk k{};
                         memcpy(k.inner, K.inner, sizeof k.inner); memcpy(k.outer, K.outer, sizeof k.outer);
                         k.kid_off = C.put_bytes(K.kid); k.kid_len = K.has_kid ? (uint32_t)K.kid.size() : GM_NONE;
+                        if (!K.n.empty()) {   // an RSA key: n then RR, on a 16-byte boundary of the limb section
+                            k.limbs = (uint32_t)K.n.size(); k.limb_off = (uint32_t)jwk_limbs.size();
+                            jwk_limbs.insert(jwk_limbs.end(), K.n.begin(), K.n.end());
+                            jwk_limbs.insert(jwk_limbs.end(), K.rr.begin(), K.rr.end());
+                        }
                         djwk.push_back(k);
                     }
                 da.first_key = ins.first->second; da.n_keys = (uint32_t)set.keys.size();
+                for (uint32_t k = 0; k < da.n_keys; k++) if (djwk[da.first_key + k].limbs) da.rsa_mask |= 1u << k;
                 std::string nm;
                 Builder::auth_token_src(L.auth.token, da.src, nm);
                 da.name_off = C.put_bytes(nm); da.name_len = (uint32_t)nm.size();
@@ -2895,6 +2942,8 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     h.off_acc_rules = I.put(acc_rules); h.off_acc_lists = I.put(acc_lists);
     h.n_auth = (uint32_t)dauth.size(); h.n_jwks = (uint32_t)djwk.size();
     h.off_auth = I.put(dauth); h.off_jwks = I.put(djwk);
+    for (const DJwk &k : djwk) if (k.limbs) h.jwt_rsa_classes |= 1u << (k.limbs == JWT_RSA_K0 ? 0 : k.limbs == JWT_RSA_K1 ? 1 : 2);
+    h.off_jwk_limbs = I.put(jwk_limbs);
     h.n_rk_cap = rkcap; h.n_rk_ids = (uint32_t)rk_ids.size(); h.n_rk_ents_keys = (uint32_t)rk_lists.size();
     h.off_rk = I.put(rk); h.off_rk_ids = I.put(rk_ids); h.off_rk_ents = I.put(rk_ents); h.off_rk_bloom = I.put(rk_bloom);
     h.n_rk_ents_n = (uint32_t)rk_ents.size();

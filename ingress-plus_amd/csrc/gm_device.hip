@@ -1802,11 +1802,13 @@ struct Scratch {
     uint32_t *d_xlen = nullptr; size_t cap_xlen = 0;
     uint8_t *d_xout = nullptr; size_t cap_xout = 0;
     // gm_auth_jwt (gm_jwt.inc): per request a work item (two uint4) and the signature's eight
-    // words, the items' order by SHA block count, control words
+    // words (an RS256 token's: its digest), the items' order by SHA block count, control words, and
+    // the RS256 tokens listed by modulus size (three lists of n)
     uint4 *d_jit0 = nullptr, *d_jit1 = nullptr; size_t cap_jit0 = 0, cap_jit1 = 0;
     uint32_t *d_jsig = nullptr; size_t cap_jsig = 0;
     uint32_t *d_jord = nullptr; size_t cap_jord = 0;
     uint32_t *d_jctl = nullptr; size_t cap_jctl = 0;
+    uint32_t *d_jrsa = nullptr; size_t cap_jrsa = 0;
     uint2 *d_rq = nullptr; size_t cap_rq = 0;            // regex-location requests deferred to k_rloc
     int32_t *d_rql = nullptr; size_t cap_rql = 0;        // and k_rloc's locations
     uint4 *d_rqs = nullptr; size_t cap_rqs = 0;          // and each one's $uri span + server (k_rloc_multi)
@@ -1866,7 +1868,7 @@ struct Scratch {
                         (void *)d_zout, (void *)d_mlim, (void *)d_mbnd, (void *)d_mlist, (void *)d_mctl, (void *)d_mtemp,
                         (void *)d_moff, (void *)d_mlen, (void *)d_mflg, (void *)d_mout, (void *)d_xlim, (void *)d_xlist, (void *)d_xctl,
                         (void *)d_xtemp, (void *)d_xoff, (void *)d_xlen, (void *)d_xout,
-                        (void *)d_jit0, (void *)d_jit1, (void *)d_jsig, (void *)d_jord, (void *)d_jctl})
+                        (void *)d_jit0, (void *)d_jit1, (void *)d_jsig, (void *)d_jord, (void *)d_jctl, (void *)d_jrsa})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
         if (h_ovlog) (void)hipHostFree(h_ovlog);
@@ -2216,7 +2218,8 @@ static int publish(gm_ctx *c, CompileResult &R, uint32_t gen, bool same_counters
         HIPCHK(c, hipMemcpy(g->d_image, R.image.data(), R.image.size(), hipMemcpyHostToDevice));
         g->tab = make_gtab(g->hdr, g->d_image, gen);
         g->jwt = JwtTab{g->hdr.n_auth ? reinterpret_cast<const DAuth *>(g->d_image + g->hdr.off_auth) : nullptr,
-                        reinterpret_cast<const DJwk *>(g->d_image + g->hdr.off_jwks), g->tab.bytes, g->hdr.n_locs, gen};
+                        reinterpret_cast<const DJwk *>(g->d_image + g->hdr.off_jwks), g->tab.bytes, g->hdr.n_locs, gen,
+                        reinterpret_cast<const uint32_t *>(g->d_image + g->hdr.off_jwk_limbs)};
         HIPCHK(c, hipMalloc((void **)&g->d_gtab, sizeof(GTab)));
         g->tab.self = g->d_gtab;
         HIPCHK(c, hipMemcpy(g->d_gtab, &g->tab, sizeof(GTab), hipMemcpyHostToDevice));
@@ -4221,7 +4224,8 @@ extern "C" int gm_auth_jwt(gm_ctx *c, const gm_batch *in, const gm_verdict *verd
     int e;
     if ((e = grow(c, s, S->d_jit0, S->cap_jit0, (size_t)n)) || (e = grow(c, s, S->d_jit1, S->cap_jit1, (size_t)n)) ||
         (e = grow(c, s, S->d_jsig, S->cap_jsig, 8 * (size_t)n)) || (e = grow(c, s, S->d_jord, S->cap_jord, (size_t)n)) ||
-        (e = grow(c, s, S->d_jctl, S->cap_jctl, (size_t)JWT_CTL_WORDS)))
+        (e = grow(c, s, S->d_jctl, S->cap_jctl, (size_t)JWT_CTL_WORDS)) ||
+        (e = grow(c, s, S->d_jrsa, S->cap_jrsa, g->hdr.jwt_rsa_classes ? 3 * (size_t)n : 1)))
         return e;
     const uint32_t blocks = (n + 255) / 256, sblocks = std::min<uint32_t>(blocks, (uint32_t)c->cu_count * 8);
     const long long now_s = (long long)std::min<uint64_t>(now, 1ull << 62);
@@ -4230,7 +4234,14 @@ extern "C" int gm_auth_jwt(gm_ctx *c, const gm_batch *in, const gm_verdict *verd
                                        S->d_jit1, S->d_jsig, S->d_jctl, out_auth);
     k_jwt_order<<<sblocks, 256, 0, s>>>(S->d_jit0, n, S->d_jctl, S->d_jord);
     // (the work items are counted on the device: a block past them exits at once)
-    k_jwt_hmac<<<blocks, 256, 0, s>>>(in->arena, S->d_jctl, S->d_jord, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt.keys, n, out_auth);
+    k_jwt_hmac<<<blocks, 256, 0, s>>>(in->arena, S->d_jctl, S->d_jord, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt.keys, n, S->d_jrsa,
+                                      out_auth);
+    // RS256: one launch per modulus size some key of the generation has, over that size's list (counted
+    // on the device like the work items).  The 16 / 24 / 32 KiB of LDS are static: no attribute to set.
+    const uint32_t rblocks = (n + 63) / 64, rcls = g->hdr.jwt_rsa_classes;
+    if (rcls & 1) k_jwt_rsa<JWT_RSA_K0, true><<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, 0, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
+    if (rcls & 2) k_jwt_rsa<JWT_RSA_K1, false><<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, 1, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
+    if (rcls & 4) k_jwt_rsa<JWT_RSA_K2, false><<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, 2, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
     k_jwt_claims<<<blocks, 256, 0, s>>>(in->arena, S->d_jctl, S->d_jord, S->d_jit0, S->d_jit1, n, now_s, out_auth);
     HIPCHK(c, hipGetLastError());
     return G.done(c);

@@ -1,4 +1,4 @@
-// gm_jwt.inc -- HS256 JWT verification for `auth_jwt` locations (NGINX Plus; nginx-plus.ingress.tmpl
+// gm_jwt.inc -- HS256 and RS256 JWT verification for `auth_jwt` locations (NGINX Plus; nginx-plus.ingress.tmpl
 // :105-111,186-188,223-228), included into gm_device.hip's anonymous namespace: gm_auth_jwt's kernels.
 //
 // THE GRAMMAR (include/gpumatch.h states the same; tests/jwt_reference.py restates it in Python).
@@ -10,23 +10,32 @@
 //   cookie, argument or header that `token=$cookie_NAME | $arg_NAME | $http_NAME` names, as nginx's
 //   variables read them.  The token is the value's bytes up to its first space or its end; none, or
 //   an empty one: DENY / NO_TOKEN.  It must be exactly three non-empty segments of [A-Za-z0-9_-]
-//   split by two '.', with no padding; segment 3 is 43 characters (32 bytes); a segment of 4k + 1
+//   split by two '.', with no padding; segment 3 is 43 characters (32 bytes) -- or, where the
+//   location's key set holds an RSA key, 342, 512 or 683 (256, 384, 512 bytes); a segment of 4k + 1
 //   characters decodes to nothing.  Anything else: DENY / MALFORMED.
 // Header and payload.  Each decodes as base64url to one JSON object (whitespace around it allowed,
 //   nothing else).  Only top-level members are read, the last of a repeated name winning:
-//     alg   a string: "HS256" goes on, "none" is DENY / ALG_NONE, any other value (one written with
-//           an escape included) DEFER / ALG; missing or not a string: MALFORMED.
+//     alg   a string: "HS256" goes on, and "RS256" where the set holds an RSA key; "none" is DENY /
+//           ALG_NONE, any other value (one written with an escape included) DEFER / ALG; missing or
+//           not a string: MALFORMED.
 //     kid   a string, optional (anything else there is ignored).
 //     exp, nbf   optional; a JSON integer ('-'? and 1..18 digits, nothing after them) or a string of
 //           1..18 decimal digits.  Anything else there: MALFORMED.
 //   Every other value is skipped: strings with their escapes honoured, objects and arrays by depth.
 //   A member name that holds a backslash is MALFORMED (deviation: nginx would unescape it; failing
 //   closed keeps an escaped "exp" from going unread).
-// Candidate keys.  The set's keys whose kid equals the token's, byte for byte, if the token has a kid
-//   and some key has that one; otherwise all keys (at most GM_JWT_KEYS).
-// Accept.  Some candidate key verifies: HMAC-SHA-256(key, segment1 "." segment2 as sent) equals the
-//   32 bytes of segment 3 (else DENY / SIGNATURE); then exp + leeway > now (else DENY / EXPIRED) and
-//   nbf <= now + leeway (else DENY / NOT_YET).  Claims are read only of a token whose signature
+// Candidate keys.  The set's keys of the alg's kind -- `oct` for HS256, RSA for RS256; an RSA key is
+//   never an HMAC key -- whose kid equals the token's, byte for byte, if the token has a kid and some
+//   key of that kind has that one; otherwise all keys of the kind (at most GM_JWT_KEYS in a set, of
+//   both kinds together).  None of the kind: DENY / SIGNATURE.
+// Accept.  Some candidate key verifies (else DENY / SIGNATURE).  HS256: segment 3 is 43 characters
+//   (else MALFORMED) and HMAC-SHA-256(key, segment1 "." segment2 as sent) equals its 32 bytes.
+//   RS256, a key whose modulus n is k bytes (256, 384, 512; e = 65537): segment 3 is ceil(4k / 3)
+//   characters; its first 8k bits, a big-endian integer s, are < n (surplus bits ignored, as for
+//   HS256); and s^65537 mod n equals, over all k bytes, the EMSA-PKCS1-v1_5 encoding
+//   00 01 FF..FF 00 | 30 31 30 0d 06 09 60 86 48 01 65 03 04 02 01 05 00 04 20 | SHA-256(segment1 "."
+//   segment2) -- nothing inside the padding is parsed.  Then exp + leeway > now (else DENY / EXPIRED)
+//   and nbf <= now + leeway (else DENY / NOT_YET).  Claims are read only of a token whose signature
 //   verified, so a forged token is always SIGNATURE, whatever its payload.
 //
 // WORK SPLIT.
@@ -49,20 +58,43 @@
 //   hash starts from the key's precomputed inner midstate and the outer hash is one compress of
 //   digest | padding from the outer midstate: blocks + 2 compresses per token.  A lane whose first
 //   candidate key fails goes round again with the next one (rare).  The compare ORs the XORs of all
-//   eight words: no early exit.
+//   eight words: no early exit.  An RS256 token runs in the same sorted launch as plain SHA-256 from
+//   the IV (no key block before it, no outer compress): its lane leaves the digest where an HS256
+//   token's signature words are and lists itself by modulus size, one atomic per (wave, size).
+// k_jwt_rsa<K> RS256's hot path, a launch per modulus size present (K = 64, 96, 128 limbs of 32 bits)
+//   over that size's list: a lane per token, 64-thread groups.  s^65537 mod n is 18 Montgomery
+//   products -- s * RR, sixteen squarings, * s (which also leaves Montgomery form) -- each K fused
+//   CIOS rows: row i adds a_i * b and m * n (m = t_0 * -1/n mod 2^32) into the accumulator t and
+//   shifts it down a limb.  The multiplicand b[K] and t[K + 1] live in VGPRs, the loop over the K
+//   limbs of a row fully unrolled so every register index is static: per limb two 32 x 32 + 64 bit
+//   multiply-adds (v_mad_u64_u32), the carries of both chains folded into the addends.  The rows are
+//   a real loop, so the multiplier a is read at a dynamic index: it lives in LDS, limb i of lane l at
+//   word 64 i + l (conflict-free; one ds_read_b32 per row, K ds_write_b32 per product) -- 16, 24 or
+//   32 KiB a wave and no other LDS.  n is read through the key pointer, four limbs a load (the lanes
+//   of a wave nearly always share the key: one line a load); for K = 64 it is held in VGPRs too.
+//   A conditional subtract per product keeps y < n.  The signature is decoded by the lane from the
+//   token's own characters (the last characters are limb 0) straight into LDS, and checked < n on the
+//   way; for the last product it is decoded again (a = s, b = y: LDS held y by then).  The compare
+//   ORs the XORs of all K limbs against the encoding built from the digest: no early exit.
 // k_jwt_claims a lane per verified token, in the same order: exp / nbf from the payload through the
 //   streaming reader, then out_auth.
 
 constexpr uint32_t JWT_BINS = 64;   // block counts 1 .. 63, and 64 or more
 // control words of one launch: [0] work items, [2 ..) the histogram, then the scatter's cursors
-constexpr uint32_t JWT_CTL_HIST = 2, JWT_CTL_CUR = JWT_CTL_HIST + JWT_BINS, JWT_CTL_WORDS = JWT_CTL_CUR + JWT_BINS;
-constexpr uint32_t JWT_VERIFIED = 0x80000000u;   // item0.x: k_jwt_hmac verified the signature
+// and the RS256 tokens of each modulus size
+constexpr uint32_t JWT_CTL_HIST = 2, JWT_CTL_CUR = JWT_CTL_HIST + JWT_BINS, JWT_CTL_RSA = JWT_CTL_CUR + JWT_BINS,
+                   JWT_CTL_WORDS = JWT_CTL_RSA + 4;
+// item0.x: the SHA block count, and above it
+constexpr uint32_t JWT_VERIFIED = 0x80000000u;   // k_jwt_hmac / k_jwt_rsa verified the signature
+constexpr uint32_t JWT_RSA = 0x40000000u;        // an RS256 token, its modulus size class (0 .. 2) at JWT_CLS_SHIFT
+constexpr uint32_t JWT_CLS_SHIFT = 28, JWT_NB_MASK = (1u << JWT_CLS_SHIFT) - 1;
 
 struct JwtTab {
     const DAuth *auth;       // per location; nullptr: the generation has no auth record
     const DJwk *keys;
     const uint8_t *bytes;
     uint32_t n_locs, gen;
+    const uint32_t *limbs;   // the RSA keys' n and RR (DJwk.limb_off)
 };
 
 __device__ __forceinline__ uint32_t jwt_code(uint32_t code, uint32_t reason) { return code | reason << 8; }
@@ -95,7 +127,7 @@ struct JwtRd {
     }
 };
 
-enum : uint32_t { JALG_MISSING, JALG_HS256, JALG_NONE, JALG_OTHER, JALG_BAD };
+enum : uint32_t { JALG_MISSING, JALG_HS256, JALG_NONE, JALG_OTHER, JALG_BAD, JALG_RS256 };
 struct JwtDoc {
     uint32_t alg, kid_mask;
     bool has_kid, has_exp, has_nbf;
@@ -180,7 +212,8 @@ __device__ bool jwt_alg(JwtRd &r, uint32_t &alg) {
         if (c == '\\') { if (r.cur < 0) return false; r.adv(); esc = true; continue; }
         if (l < 4) v0 |= (uint32_t)c << (8 * l); else if (l < 8) v1 |= (uint32_t)c << (8 * (l - 4));
     }
-    alg = esc ? JALG_OTHER : l == 5 && v0 == 0x35325348u && v1 == '6' ? JALG_HS256 : l == 4 && v0 == 0x656E6F6Eu ? JALG_NONE : JALG_OTHER;
+    alg = esc ? JALG_OTHER : l == 5 && v0 == 0x35325348u && v1 == '6' ? JALG_HS256 : l == 5 && v0 == 0x35325352u && v1 == '6' ? JALG_RS256 :
+          l == 4 && v0 == 0x656E6F6Eu ? JALG_NONE : JALG_OTHER;
     return true;
 }
 // one JSON object's top-level members: alg and kid of a header, exp and nbf of a payload
@@ -285,14 +318,33 @@ __device__ uint32_t jwt_find(const uint8_t *A, uint64_t len, const gm_req *rp, c
             if (d1 == GM_NONE) d1 = k; else if (d2 == GM_NONE) d2 = k; else return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
         } else if (!jwt_b64ok(c)) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
     }
-    if (d2 == GM_NONE || d1 == 0 || d2 == d1 + 1 || tl - d2 - 1 != 43 || (d1 & 3) == 1 || ((d2 - d1 - 1) & 3) == 1)
+    const uint32_t sl = tl - d2 - 1;   // segment 3 (if there is one)
+    const bool sl_ok = sl == 43 || (a.rsa_mask && (sl == jwt_rsa_chars(JWT_RSA_K0) || sl == jwt_rsa_chars(JWT_RSA_K1) || sl == jwt_rsa_chars(JWT_RSA_K2)));
+    if (d2 == GM_NONE || d1 == 0 || d2 == d1 + 1 || !sl_ok || (d1 & 3) == 1 || ((d2 - d1 - 1) & 3) == 1)
         return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
     JwtRd rd;
     JwtDoc d;
     rd.init(T, d1);
     if (!jwt_walk(rd, true, t, a, d) || d.alg == JALG_MISSING || d.alg == JALG_BAD) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
     if (d.alg == JALG_NONE) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_ALG_NONE);
+    const uint32_t slen = d2, all = (1u << a.n_keys) - 1;   // slen: segment1 "." segment2
+    if (d.alg == JALG_RS256 && a.rsa_mask) {
+        // the RSA keys, narrowed by kid, that are of the size segment 3 has; the signature stays in the text
+        uint32_t cand = all & a.rsa_mask, fit = 0;
+        if (d.has_kid && (d.kid_mask & cand)) cand &= d.kid_mask;
+        const uint32_t cls = sl == jwt_rsa_chars(JWT_RSA_K0) ? 0u : sl == jwt_rsa_chars(JWT_RSA_K1) ? 1u : 2u;
+        for (uint32_t k = 0; k < a.n_keys; k++)
+            if ((cand >> k & 1) && sl != 43 && t.keys[a.first_key + k].limbs == jwt_rsa_k(cls)) fit |= 1u << k;
+        if (!fit) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
+        it0 = make_uint4((slen + 9 + 63) / 64 | JWT_RSA | cls << JWT_CLS_SHIFT, slen, (uint32_t)vo, (uint32_t)(vo >> 32));
+        it1 = make_uint4(a.first_key, fit, d1 + 1, a.leeway);
+        return GM_NONE;
+    }
     if (d.alg != JALG_HS256) return jwt_code(GM_AUTH_DEFER, GM_AUTH_R_ALG);
+    if (sl != 43) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
+    uint32_t cand = all & ~a.rsa_mask;
+    if (!cand) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
+    if (d.has_kid && (d.kid_mask & cand)) cand &= d.kid_mask;
     // segment 3: 43 characters = 258 bits, the first 256 of them as eight big-endian words
     unsigned long long acc = 0;
     for (uint32_t k = 0, bits = 0, wi = 0; k < 43; k++) {
@@ -300,9 +352,8 @@ __device__ uint32_t jwt_find(const uint8_t *A, uint64_t len, const gm_req *rp, c
         bits += 6;
         if (bits >= 32) { bits -= 32; sig[wi++] = (uint32_t)(acc >> bits); }
     }
-    const uint32_t slen = d2;   // segment1 "." segment2
     it0 = make_uint4((slen + 9 + 63) / 64, slen, (uint32_t)vo, (uint32_t)(vo >> 32));
-    it1 = make_uint4(a.first_key, d.has_kid && d.kid_mask ? d.kid_mask : (1u << a.n_keys) - 1, d1 + 1, a.leeway);
+    it1 = make_uint4(a.first_key, cand, d1 + 1, a.leeway);
     return GM_NONE;
 }
 
@@ -330,7 +381,7 @@ __global__ __launch_bounds__(256) void k_jwt_find(const gm_req *__restrict__ req
             if (code != GM_NONE) { out_auth[i] = code; it0.x = 0; }
             else item1[i] = it1;
             item0[i] = it0;
-            nb = it0.x;
+            nb = it0.x & JWT_NB_MASK;
         }
         jwt_bin_add(ctl + JWT_CTL_HIST, min(nb, JWT_BINS) - 1, nb != 0);
     }
@@ -353,7 +404,7 @@ __global__ __launch_bounds__(256) void k_jwt_order(const uint4 *__restrict__ ite
     __syncthreads();
     for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < n; i0 += gridDim.x * blockDim.x) {
         const uint32_t i = i0 + threadIdx.x;
-        const uint32_t nb = i < n ? item0[i].x : 0u;
+        const uint32_t nb = i < n ? item0[i].x & JWT_NB_MASK : 0u;
         const uint32_t bin = min(nb, JWT_BINS) - 1;
         const uint32_t pos = jwt_bin_add(ctl + JWT_CTL_CUR, bin, nb != 0);
         if (nb) order[min(base[bin & (JWT_BINS - 1)] + pos, n - 1)] = i;
@@ -377,15 +428,18 @@ __device__ __forceinline__ void sha256_compress(uint32_t (&H)[8], uint32_t (&w)[
     H[0] += a; H[1] += b; H[2] += c; H[3] += d; H[4] += e; H[5] += f; H[6] += g; H[7] += h;
 }
 
-__global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A, const uint32_t *__restrict__ ctl,
+__global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A, uint32_t *__restrict__ ctl,
                                                   const uint32_t *__restrict__ order, uint4 *__restrict__ item0,
-                                                  const uint4 *__restrict__ item1, const uint32_t *__restrict__ sig,
-                                                  const DJwk *__restrict__ keys, uint32_t n, uint32_t *__restrict__ out_auth) {
+                                                  const uint4 *__restrict__ item1, uint32_t *__restrict__ sig,
+                                                  const DJwk *__restrict__ keys, uint32_t n, uint32_t *__restrict__ rlist,
+                                                  uint32_t *__restrict__ out_auth) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= min(ctl[0], n)) return;
     const uint32_t i = min(order[gid], n - 1);
     const uint4 it0 = item0[i], it1 = item1[i];
-    const uint32_t nb = it0.x, len = it0.y;
+    const uint32_t nb = it0.x & JWT_NB_MASK, len = it0.y;
+    const bool rsa = it0.x & JWT_RSA;   // plain SHA-256 of the signing input: the digest is k_jwt_rsa's
+    const uint32_t bits = ((rsa ? 0u : 64u) + len) * 8u;   // (an HMAC's key block came first)
     const uint64_t text = (uint64_t)it0.z | (uint64_t)it0.w << 32;
     const uint32_t s = (uint32_t)text & 3u, sel = 0x00010203u + 0x01010101u * s;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(A + (text - s));   // the dword that holds text byte 0
@@ -397,6 +451,10 @@ __global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A,
         {
             const uint4 p = reinterpret_cast<const uint4 *>(K->inner)[0], q = reinterpret_cast<const uint4 *>(K->inner)[1];
             H[0] = p.x; H[1] = p.y; H[2] = p.z; H[3] = p.w; H[4] = q.x; H[5] = q.y; H[6] = q.z; H[7] = q.w;
+        }
+        if (rsa) {
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) H[j] = SHA256_IV[j];
         }
         for (uint32_t b = 0; b < nb; b++) {
             const uint32_t *blk = src + 16 * b;
@@ -422,9 +480,14 @@ __global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A,
                     }
                     w[j] = x;
                 }
-                if (b + 1 == nb) { w[14] = 0; w[15] = (64u + len) * 8u; }   // (the key block came first)
+                if (b + 1 == nb) { w[14] = 0; w[15] = bits; }
             }
             sha256_compress(H, w);
+        }
+        if (rsa) {
+            reinterpret_cast<uint4 *>(sig + 8 * (size_t)i)[0] = make_uint4(H[0], H[1], H[2], H[3]);
+            reinterpret_cast<uint4 *>(sig + 8 * (size_t)i)[1] = make_uint4(H[4], H[5], H[6], H[7]);
+            break;
         }
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++) w[j] = H[j];
@@ -441,7 +504,133 @@ __global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A,
                               (H[4] ^ g1.x) | (H[5] ^ g1.y) | (H[6] ^ g1.z) | (H[7] ^ g1.w);
         ok = diff == 0;
     }
-    if (ok) item0[i].x = nb | JWT_VERIFIED;
+    const uint32_t cls = it0.x >> JWT_CLS_SHIFT & 3u;
+    const uint32_t pos = jwt_bin_add(ctl + JWT_CTL_RSA, cls, rsa);
+    if (rsa) rlist[(size_t)min(cls, 2u) * n + min(pos, n - 1)] = i;
+    else if (ok) item0[i].x = nb | JWT_VERIFIED;
+    else out_auth[i] = jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
+}
+
+// The K-limb integer s that segment 3 (S: jwt_rsa_chars(K) characters) begins with, least significant
+// limb first, into the lane's LDS column a[64 j]; whether s < n.  Limb j is stream bits
+// [32 (K - 1 - j), 32 (K - j)): at most seven characters, all of them the segment's.
+template <uint32_t K>
+__device__ bool jwt_rsa_sig(const uint8_t *S, const uint32_t *__restrict__ nn, uint32_t *a) {
+    uint32_t bw = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < K; j++) {
+        const uint32_t lo = 32 * (K - 1 - j), c1 = (lo + 31) / 6;
+        unsigned long long acc = 0;
+        for (uint32_t c = lo / 6; c <= c1; c++) acc = acc << 6 | jwt_b64v(S[c]);
+        const uint32_t v = (uint32_t)(acc >> (6 * (c1 + 1) - (lo + 32)));
+        a[64 * j] = v;
+        bw = (uint32_t)(((uint64_t)v - nn[j] - bw) >> 63);
+    }
+    return bw != 0;
+}
+
+// limb j of the EMSA-PKCS1-v1_5 encoding of a SHA-256 digest (eight big-endian words d), K limbs in all
+template <uint32_t K>
+__device__ __forceinline__ uint32_t jwt_rsa_em(const uint32_t (&d)[8], uint32_t j) {
+    constexpr uint32_t di[5] = {0x05000420u, 0x03040201u, 0x86480165u, 0x0D060960u, 0x00303130u};   // DigestInfo, 00 before it
+    return j < 8 ? d[7 - j] : j < 13 ? di[j - 8] : j + 1 < K ? 0xFFFFFFFFu : 0x0001FFFFu;
+}
+
+template <uint32_t K, bool NREG>   // NREG: n in VGPRs as well (else four limbs a load, every row)
+__global__ __launch_bounds__(64) void k_jwt_rsa(const uint8_t *__restrict__ A, const uint32_t *__restrict__ ctl,
+                                                const uint32_t *__restrict__ rlist, uint32_t cls, uint4 *__restrict__ item0,
+                                                const uint4 *__restrict__ item1, const uint32_t *__restrict__ dig, JwtTab t,
+                                                uint32_t n, uint32_t *__restrict__ out_auth) {
+    __shared__ uint32_t lds[K * 64];
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+    if (gid >= min(ctl[JWT_CTL_RSA + cls], n)) return;
+    const uint32_t i = min(rlist[(size_t)cls * n + gid], n - 1);
+    const uint4 it0 = item0[i], it1 = item1[i];
+    const uint8_t *S = A + ((uint64_t)it0.z | (uint64_t)it0.w << 32) + it0.y + 1;   // segment 3
+    uint32_t *a = lds + threadIdx.x;
+    uint32_t d[8];
+    {
+        const uint4 p = reinterpret_cast<const uint4 *>(dig + 8 * (size_t)i)[0], q = reinterpret_cast<const uint4 *>(dig + 8 * (size_t)i)[1];
+        d[0] = p.x; d[1] = p.y; d[2] = p.z; d[3] = p.w; d[4] = q.x; d[5] = q.y; d[6] = q.z; d[7] = q.w;
+    }
+    bool ok = false;
+    for (uint32_t m = it1.y & ((1u << JWT_KEYS_MAX) - 1); m && !ok; m &= m - 1) {
+        const DJwk *J = t.keys + it1.x + (uint32_t)__builtin_ctz(m);
+        if (J->limbs != K) continue;
+        const uint32_t *nn = t.limbs + J->limb_off;   // n[K], RR[K]: 16-byte aligned
+        const uint4 *nq = reinterpret_cast<const uint4 *>(nn);
+        const uint32_t n0 = J->inner[0];
+        if (!jwt_rsa_sig<K>(S, nn, a)) continue;      // a = s, and s < n
+        uint32_t b[K], tt[K + 1], nr[NREG ? K : 16];
+#pragma unroll
+        for (uint32_t j = 0; j < K; j += 4) {         // b = RR
+            const uint4 v = nq[(K + j) / 4];
+            b[j] = v.x; b[j + 1] = v.y; b[j + 2] = v.z; b[j + 3] = v.w;
+            if (NREG) { const uint4 u = nq[j / 4]; nr[j] = u.x; nr[j + 1] = u.y; nr[j + 2] = u.z; nr[j + 3] = u.w; }
+        }
+        // n's limb j: from the registers, or from a ring of four loads (16 limbs) that runs three loads
+        // ahead of the limb in use and on into the next row (K / 4 is a multiple of 4)
+#define JWT_RSA_N(j) nr[NREG ? (j) : (j) & 15]
+#define JWT_RSA_NLOAD(g) \
+        { const uint4 u = nq[(g) % (K / 4)]; nr[(g) % 4 * 4] = u.x; nr[(g) % 4 * 4 + 1] = u.y; nr[(g) % 4 * 4 + 2] = u.z; nr[(g) % 4 * 4 + 3] = u.w; }
+#pragma unroll 1
+        for (uint32_t r = 0; r < 18; r++) {           // y = mont(a, b): s RR, sixteen squarings, y s
+#pragma unroll
+            for (uint32_t j = 0; j <= K; j++) tt[j] = 0;
+            if (!NREG) { JWT_RSA_NLOAD(0) JWT_RSA_NLOAD(1) JWT_RSA_NLOAD(2) }
+#pragma unroll 1
+            for (uint32_t row = 0; row < K; row++) {
+                const uint32_t ai = a[64 * row];
+                uint32_t mq = 0;
+                uint64_t x = 0, y = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < K; j++) {
+                    // the addends, carries folded in, are opaque to the compiler: each multiply-add then waits
+                    // for its chain (left free, all K products a_i b[j] + t[j] are formed ahead: K more VGPRs),
+                    // and at each fourth limb the load of the ring's next four is held to this place
+                    uint64_t ax = (uint64_t)tt[j] + (uint32_t)(x >> 32);
+                    if (!NREG && (j & 3) == 0) {
+                        asm volatile("" : "+v"(ax) : : "memory");
+                        JWT_RSA_NLOAD(j / 4 + 3)
+                    } else asm("" : "+v"(ax));
+                    x = (uint64_t)ai * b[j] + ax;
+                    if (j == 0) mq = (uint32_t)x * n0;
+                    uint64_t ay = (uint64_t)(uint32_t)x + (uint32_t)(y >> 32);
+                    asm("" : "+v"(ay));
+                    y = (uint64_t)mq * JWT_RSA_N(j) + ay;
+                    if (j) tt[j - 1] = (uint32_t)y;   // (limb 0 is zero: that is what m was chosen for)
+                }
+                const uint64_t z = (uint64_t)tt[K] + (x >> 32) + (y >> 32);
+                tt[K - 1] = (uint32_t)z; tt[K] = (uint32_t)(z >> 32);
+            }
+            // t < 2 n: subtract n once if t >= n (the borrow of t - n first, then the subtraction)
+            if (!NREG) asm volatile("" ::: "memory");   // (n's loads below stay below the rows)
+            uint32_t bw = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < K; j++) bw = (uint32_t)(((uint64_t)tt[j] - (NREG ? nr[NREG ? j : 0] : nn[j]) - bw) >> 63);
+            const uint32_t sub = (tt[K] | (bw ^ 1u)) ? 0xFFFFFFFFu : 0u;
+            bw = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < K; j++) {
+                const uint64_t v = (uint64_t)tt[j] - ((NREG ? nr[NREG ? j : 0] : nn[j]) & sub) - bw;
+                b[j] = (uint32_t)v;
+                bw = (uint32_t)(v >> 63);
+            }
+            // the next multiplier: y, and s for the last product (b = y either way)
+            if (r == 16) jwt_rsa_sig<K>(S, nn, a);
+            else if (r < 16) {
+#pragma unroll
+                for (uint32_t j = 0; j < K; j++) a[64 * j] = b[j];
+            }
+        }
+#undef JWT_RSA_N
+#undef JWT_RSA_NLOAD
+        uint32_t diff = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) diff |= b[j] ^ jwt_rsa_em<K>(d, j);
+        ok = diff == 0;
+    }
+    if (ok) item0[i].x = it0.x | JWT_VERIFIED;
     else out_auth[i] = jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
 }
 

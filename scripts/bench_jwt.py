@@ -8,7 +8,13 @@ after k_jwt_find (DEFER), so the find + order share of the call is known and the
 share follows by difference.  Python's single-thread hmac over the same tokens is timed as context.
 Prints one JSON line.
 
+`--alg RS256` is the RSA leg instead: one 2048-bit key (tests/golden/jwt/rsa-2048), 512 distinct tokens
+cycled over the batch (a tenth of them forged), verified by k_jwt_rsa (a lane per token, Montgomery
+products); outcomes are compared with tests/jwt_rsa_reference.py on the distinct tokens, the same
+batch saying RS384 gives the find + order share, and the restatement's own pow() is timed as context.
+
     python scripts/bench_jwt.py [--n 1000000] [--reps 10] [--warmup 3] [--large 0.1]
+    python scripts/bench_jwt.py --alg RS256 [--n 65536]
 """
 
 import argparse
@@ -26,6 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "ingress-plus_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import jwt_reference as ref  # noqa: E402
+import jwt_rsa_reference as rsa  # noqa: E402
 from gpumatch import blob, engine, records  # noqa: E402
 
 KEY = b"fantasticjwt"
@@ -62,8 +69,55 @@ def batch(n, toks):
     return rq, arena
 
 
+def timed(e, a, dev, toks, n):
+    """(ms of each repeat, out_auth) of gm_auth_jwt over n requests that cycle through toks."""
+    import torch
+    rq, arena = batch(n, toks)
+    ver = np.zeros(n, dtype=records.VERDICT_DTYPE)
+    ver["gen"], ver["location_id"] = 1, 0
+    d_ver = torch.from_numpy(ver.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_out = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_rq = torch.from_numpy(rq.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_ar = torch.from_numpy(arena).to(dev)
+    ms = []
+    for k in range(a.warmup + a.reps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        e.auth_jwt_ptr(d_rq.data_ptr(), d_ar.data_ptr(), len(arena), n, d_ver.data_ptr(), NOW, d_out.data_ptr(), 0)
+        t1.record()
+        e.sync(0)
+        t1.synchronize()
+        if k >= a.warmup:
+            ms.append(t0.elapsed_time(t1))
+    return ms, d_out.cpu().numpy().view(np.uint32)
+
+
+def rsa_leg(a, e, dev):
+    n = a.n if a.n != 1_000_000 else 65536
+    nn, d, pub = rsa.fixture_key("rsa-2048", "0001")
+    e.load(blob.make_blob(None, {"c": CONF}, jwks={"/k": json.dumps({"keys": [pub]})}), 1)
+    res = {}
+    for alg in ("RS256", "RS384"):
+        toks = [rsa.sign(nn, d, {"typ": "JWT", "alg": alg, "kid": "0001"}, {"sub": "q%05x" % i, "iss": "My API Gateway"}, add=i % 10 == 9)
+                for i in range(512)]
+        ms, got = timed(e, a, dev, toks, n)
+        t0 = time.perf_counter()
+        want = np.array([rsa.outcome(t, [("0001", nn)], NOW) for t in toks], dtype=np.uint32)
+        cpu_s = (time.perf_counter() - t0) / len(toks)
+        assert np.array_equal(got, want[np.arange(n) % len(toks)]), alg
+        res[alg] = (float(np.median(ms)), ms, cpu_s)
+    med, ms, cpu_s = res["RS256"]
+    rsa_ms = med - res["RS384"][0]
+    print(json.dumps({"bench": "jwt_rs256", "n": n, "modulus_bits": 2048, "distinct_tokens": 512, "ms_median": round(med, 4),
+                      "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "reps": a.reps, "tokens_per_s": round(n / med * 1e3),
+                      "ms_find_order_median": round(res["RS384"][0], 4), "ms_hash_rsa_claims_by_difference": round(rsa_ms, 4),
+                      "montgomery_products_per_s": round(18 * n / rsa_ms * 1e3), "multiply_adds_per_s": round(18 * 2 * 64 * 64 * n / rsa_ms * 1e3),
+                      "python_restatement_tokens_per_s_one_thread": round(1 / cpu_s), "csrc_hash": engine.build_hash()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--alg", choices=["HS256", "RS256"], default="HS256")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -73,6 +127,8 @@ def main():
     assert torch.cuda.is_available(), "bench_jwt.py needs a GPU"
     dev = torch.device("cuda", 0)
     e = engine.Engine(0)
+    if a.alg == "RS256":
+        return rsa_leg(a, e, dev)
     e.load(blob.make_blob(None, {"c": CONF}, jwks={"/k": json.dumps({"keys": [{"kty": "oct", "k": ref.b64e(KEY), "kid": "0001"}]})}), 1)
     assert e.stats()["n_auth_locations"] == 1
     ver = np.zeros(a.n, dtype=records.VERDICT_DTYPE)
