@@ -202,10 +202,16 @@ enum { GM_WAF_OFF = 0, GM_WAF_MONITORING = 1, GM_WAF_SAFE_BLOCKING = 2, GM_WAF_B
  * may mix `oct` keys and RSA public keys {"kty":"RSA","n":"<base64url>","e":"AQAB","kid":"..."}: e must
  * decode to 65537 (leading zero bytes allowed) and n, leading zero bytes stripped, must be odd and
  * exactly 2048, 3072 or 4096 bits long; every other member is skipped (a private JWK's d, p, q are
- * never stored).  With it
+ * never stored).  It may also hold P-256 public keys {"kty":"EC","crv":"P-256","x":"<base64url>",
+ * "y":"<base64url>","kid":"..."}: x and y must decode to exactly 32 bytes each, both below the field
+ * prime p, and satisfy y^2 = x^3 - 3x + b (mod p); further members (d, use, alg) are skipped and never
+ * stored.  Any other crv, length or an off-curve point fails the whole set, as an RSA key with e = 3
+ * does.  (Deviation: a key Q for which i G + j Q, i, j in 0 .. 3, is the point at infinity is not taken
+ * either -- only Q = c G for a handful of c = -i / j, keys whose private half is public knowledge.)
+ * With it
  * the compiler accepts `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME | $http_NAME]` at server
  * or location level iff the auth_jwt_key_file in effect names such an entry, the entry parses, all
- * its keys are such `oct` or RSA keys, and an `error_page 401` beside it names a location of the template's
+ * its keys are such `oct`, RSA or EC keys, and an `error_page 401` beside it names a location of the template's
  * shape (`internal; return 302 <url>;`).  In every other case the directive is rejected as before
  * (a blob without the entry compiles as it always did).  Supplying the entry is the caller's promise
  * to run gm_auth_jwt on the verdicts (below). */
@@ -554,7 +560,7 @@ int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_
                           uint64_t *out_off, uint32_t *out_len, void *stream);
 
 /* ---------------------------------------------------------------- auth_jwt (NGINX Plus)
- * HS256 and RS256 JWT verification for the locations `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME |
+ * HS256, RS256 and ES256 JWT verification for the locations `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME |
  * $http_NAME]` protects (nginx-plus.ingress.tmpl:105-111,186-188,223-228; the nginx.com/jwt-key,
  * jwt-realm, jwt-token and jwt-login-url annotations).  The key file is a GM_ENTRY_JWK entry of the
  * blob; the compiler accepts the directive only then (see GM_ENTRY_JWK).  gm_match_batch does not
@@ -571,19 +577,19 @@ int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_
  *    argument's or header's as nginx's variable reads it.  The token is its bytes up to the first
  *    space or the value's end (none, or empty: NO_TOKEN).  It must be exactly three non-empty
  *    segments of [A-Za-z0-9_-] split by two '.', with no padding; segment 3 is 43 characters (32
- *    bytes) -- or, where the location's set holds an RSA key, 342, 512 or 683; no segment is 4k + 1
- *    characters long.  Anything else: MALFORMED.
+ *    bytes) -- or, where the location's set holds an RSA key, 342, 512 or 683, or, where it holds an
+ *    EC key, 86 (r | s, 64 bytes); no segment is 4k + 1 characters long.  Anything else: MALFORMED.
  *  - Header and payload decode as base64url to one JSON object each (whitespace around it allowed).
  *    Top-level members only, the last of a repeated name winning: alg (a string: "HS256" goes on,
- *    and "RS256" where the set holds an RSA key; "none" is ALG_NONE, any other value DEFER; missing
+ *    "RS256" where the set holds an RSA key and "ES256" where it holds an EC key; "none" is ALG_NONE, any other value DEFER; missing
  *    or not a string: MALFORMED), kid (a string,
  *    optional), exp and nbf (optional; a JSON integer of 1..18 digits with an optional '-', or a
  *    string of 1..18 decimal digits, as the reference's own minion token writes it; anything else
  *    there: MALFORMED).  Nested values and strings are skipped with escapes honoured.  A member NAME
  *    holding a backslash is MALFORMED (nginx would unescape it: the engine fails closed).
- *  - Candidate keys: the set's keys of the alg's kind (`oct` for HS256, RSA for RS256: an RSA key is
- *    never an HMAC key) whose kid equals the token's, if the token has a kid and any key of the kind
- *    has that one; otherwise all keys of the kind (the first GM_JWT_KEYS of a set are read, of both
+ *  - Candidate keys: the set's keys of the alg's kind (`oct` for HS256, RSA for RS256, EC for ES256: an
+ *    RSA or EC key is never an HMAC key) whose kid equals the token's, if the token has a kid and any key of the kind
+ *    has that one; otherwise all keys of the kind (the first GM_JWT_KEYS of a set are read, of all
  *    kinds together).  No key of the kind: SIGNATURE.
  *  - Accept: some candidate key verifies (else SIGNATURE).  HS256: segment 3 is 43 characters (else
  *    MALFORMED) and HMAC-SHA-256 over the ASCII text segment1 "." segment2 as sent equals its bytes.
@@ -591,9 +597,15 @@ int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_
  *    bits as a big-endian integer s are < n (surplus bits ignored, as for HS256), and s^65537 mod n
  *    equals, over all k bytes, the EMSA-PKCS1-v1_5 encoding 00 01 FF..FF 00 | 30 31 30 0d 06 09 60 86
  *    48 01 65 03 04 02 01 05 00 04 20 | SHA-256(segment1 "." segment2); nothing inside the padding is
- *    parsed.  Then exp + leeway > now (else EXPIRED) and nbf <= now + leeway (else NOT_YET).  Claims
+ *    parsed.  ES256 (ECDSA over P-256, group order n): segment 3 is 86 characters (HS256 with 86 is
+ *    MALFORMED as with an RSA length; ES256 with another admitted length, or RS256 with 86, SIGNATURE);
+ *    its first 512 bits are r | s, two big-endian 256-bit integers (the 4 surplus bits ignored) with
+ *    1 <= r, s < n; with e = SHA-256(segment1 "." segment2) as an integer, w = 1/s, u1 = e w, u2 = r w
+ *    (mod n) and R = u1 G + u2 Q, R is not the point at infinity and x_R mod n = r.  High s is accepted
+ *    (JWS has no low-s rule).  Then exp + leeway > now (else EXPIRED) and nbf <= now + leeway (else NOT_YET).  Claims
  *    are read only once the signature verified.
- *    A location whose set holds no RSA key answers every input exactly as before RS256 was known.
+ *    A location whose set holds no RSA key answers every input exactly as before RS256 was known, and
+ *    one whose set holds no EC key as before ES256 was (ES256 DEFER / ALG, 86 characters MALFORMED).
  * out_auth[i] = code | reason << 8.  All pointers are device pointers (verdicts and in->reqs 16-byte
  * aligned); `now` is Unix seconds; asynchronous on `stream`, completed by gm_sync, like
  * gm_upstream_uris. */
@@ -611,7 +623,7 @@ enum {
     GM_AUTH_R_SIGNATURE = 4,   /* DENY: no candidate key verifies                                 */
     GM_AUTH_R_EXPIRED   = 5,   /* DENY: exp + leeway <= now                                       */
     GM_AUTH_R_NOT_YET   = 6,   /* DENY: nbf > now + leeway                                        */
-    GM_AUTH_R_ALG       = 7,   /* DEFER: alg is anything but HS256, or RS256 where the set has an RSA key */
+    GM_AUTH_R_ALG       = 7,   /* DEFER: alg is anything but HS256, RS256 where the set has an RSA key, ES256 where it has an EC key */
     GM_AUTH_R_STALE     = 8    /* DEFER: the verdict is from another generation (or its record leaves the arena) */
 };
 int         gm_auth_jwt(gm_ctx *ctx, const gm_batch *in, const gm_verdict *verdicts, uint64_t now,

@@ -20,6 +20,7 @@
 #include <unordered_map>
 
 #include "gm_inet.hpp"
+#include "gm_p256.hpp"
 #include "gm_regex.hpp"
 
 namespace gm {
@@ -141,6 +142,7 @@ uint32_t decoder_bit(const std::string &name) {
 struct JwkKey {
     std::string kid; bool has_kid = false; uint32_t inner[8], outer[8];
     std::vector<uint32_t> n, rr;   // an RSA key (n not empty): gm_tables.hpp DJwk; n0inv in inner[0]
+    std::vector<uint32_t> ec;      // a P-256 key (not empty): its table, gm_p256.hpp
 };
 struct JwkSet { bool ok = false; std::vector<JwkKey> keys; };   // ok: parses, every key `oct` or an RSA key the engine takes
 struct AuthIR {
@@ -293,9 +295,69 @@ static bool rsa_key(const std::string &nb, const std::string &eb, JwkKey &K) {
     K.inner[0] = 0u - inv;
     return true;
 }
-// {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} | {"kty":"RSA","n":"...","e":"AQAB","kid":"..."} ...]}:
-// the first JWT_KEYS_MAX keys are taken; every key must be `oct` with a non-empty k, or an RSA key
-// rsa_key takes (any further member -- a private JWK's d, p, q -- is skipped and never stored)
+// P-256 points on the host, affine and in Montgomery form (gm_p256.hpp), with an addition that is complete:
+// either operand at infinity, equal operands (a doubling: T[1][1] of the key Q = G) and opposite ones.
+struct EcPt { p256::Fe x, y; bool inf; };
+static p256::Fe fe_inv(const p256::Fe &a) {   // a^(p - 2)
+    p256::Fe r = p256::fe_one();
+    for (int i = 255; i >= 0; i--) {
+        r = p256::fe_sqr(r);
+        if ((p256::P(i / 32) - (i < 32 ? 2u : 0u)) >> (i % 32) & 1) r = p256::fe_mul(r, a);
+    }
+    return r;
+}
+static EcPt ec_add(const EcPt &a, const EcPt &b) {
+    using namespace p256;
+    if (a.inf) return b;
+    if (b.inf) return a;
+    Fe lam;
+    if (!fe_diff(a.x, b.x)) {
+        if (fe_diff(a.y, b.y) || !fe_or(a.y)) return EcPt{a.x, a.y, true};
+        const Fe t = fe_sub(fe_sqr(a.x), fe_one());   // (3 x^2 - 3) / 2 y
+        lam = fe_mul(fe_add(fe_add(t, t), t), fe_inv(fe_add(a.y, a.y)));
+    } else lam = fe_mul(fe_sub(b.y, a.y), fe_inv(fe_sub(b.x, a.x)));
+    EcPt r;
+    r.x = fe_sub(fe_sub(fe_sqr(lam), a.x), b.x);
+    r.y = fe_sub(fe_mul(lam, fe_sub(a.x, r.x)), a.y);
+    r.inf = false;
+    return r;
+}
+// A P-256 public key the engine takes: x and y of exactly 32 bytes, both < p, on the curve y^2 = x^3 - 3 x + b,
+// and no entry of its table i G + j Q (i, j in 0 .. 3) at infinity -- that refuses only Q = c G for a handful
+// of tiny c, keys whose private half is public knowledge.  Fills the table (gm_tables.hpp DJwk).
+static bool ec_key(const std::string &xb, const std::string &yb, JwkKey &K) {
+    using namespace p256;
+    if (xb.size() != 32 || yb.size() != 32) return false;
+    Fe x{}, y{}, rr, b;
+    EcPt g;
+    g.inf = false;
+    for (uint32_t i = 0; i < 32; i++) {
+        x.v[i / 4] |= (uint32_t)(uint8_t)xb[31 - i] << (8 * (i % 4));
+        y.v[i / 4] |= (uint32_t)(uint8_t)yb[31 - i] << (8 * (i % 4));
+    }
+    for (uint32_t j = 0; j < 8; j++) { rr.v[j] = RR(j); b.v[j] = CB(j); g.x.v[j] = GX(j); g.y.v[j] = GY(j); }
+    if (!lt_p(x) || !lt_p(y)) return false;
+    const EcPt q{fe_mul(x, rr), fe_mul(y, rr), false};
+    const Fe x3 = fe_mul(fe_sqr(q.x), q.x), x2 = fe_add(q.x, q.x);
+    if (fe_diff(fe_sqr(q.y), fe_add(fe_sub(x3, fe_add(x2, q.x)), b))) return false;
+    EcPt gm[4], qm[4];
+    gm[0] = qm[0] = EcPt{g.x, g.y, true};
+    for (int i = 1; i < 4; i++) { gm[i] = ec_add(gm[i - 1], g); qm[i] = ec_add(qm[i - 1], q); }
+    K.ec.clear();
+    for (int i = 0; i < 4; i++)
+        for (int j = i ? 0 : 1; j < 4; j++) {
+            const EcPt t = ec_add(gm[i], qm[j]);
+            if (t.inf) return false;
+            K.ec.insert(K.ec.end(), t.x.v, t.x.v + 8);
+            K.ec.insert(K.ec.end(), t.y.v, t.y.v + 8);
+        }
+    memset(K.inner, 0, sizeof K.inner); memset(K.outer, 0, sizeof K.outer);
+    return true;
+}
+// {"keys":[{"kty":"oct","k":"<base64url>","kid":"..."} | {"kty":"RSA","n":"...","e":"AQAB","kid":"..."} |
+// {"kty":"EC","crv":"P-256","x":"...","y":"...","kid":"..."} ...]}: the first JWT_KEYS_MAX keys are taken; every
+// key must be `oct` with a non-empty k, an RSA key rsa_key takes or an EC key ec_key takes (any further member
+// -- a private JWK's d, p, q -- is skipped and never stored)
 static JwkSet parse_jwks(const char *data, size_t len) {
     JwkSet S;
     Json J{data, data + len};
@@ -310,7 +372,7 @@ static JwkSet parse_jwks(const char *data, size_t len) {
             have = true;
             if (J.lit(']')) continue;
             do {
-                std::string kty, kv, kid, kn, ke;
+                std::string kty, kv, kid, kn, ke, crv, kx, ky;
                 bool has_kid = false;
                 if (!J.lit('{')) return S;
                 if (!J.lit('}')) {
@@ -321,6 +383,7 @@ static JwkSet parse_jwks(const char *data, size_t len) {
                         else if (m == "k") { if (!J.str(kv)) return S; }
                         else if (m == "kid") { if (!J.str(kid)) return S; has_kid = true; }
                         else if ((m == "n" || m == "e") && (J.ws(), J.p < J.e && *J.p == '"')) { if (!J.str(m == "n" ? kn : ke)) return S; }
+                        else if ((m == "crv" || m == "x" || m == "y") && (J.ws(), J.p < J.e && *J.p == '"')) { if (!J.str(m == "crv" ? crv : m == "x" ? kx : ky)) return S; }
                         else if (!J.skip()) return S;
                     } while (J.lit(','));
                     if (!J.lit('}')) return S;
@@ -330,6 +393,8 @@ static JwkSet parse_jwks(const char *data, size_t len) {
                 K.kid = kid; K.has_kid = has_kid;
                 if (kty == "RSA") {
                     if (!b64url_decode(kn, nb) || !b64url_decode(ke, eb) || !rsa_key(nb, eb, K)) return S;
+                } else if (kty == "EC") {
+                    if (crv != "P-256" || !b64url_decode(kx, nb) || !b64url_decode(ky, eb) || !ec_key(nb, eb, K)) return S;
                 } else {
                     if (kty != "oct" || !b64url_decode(kv, key) || key.empty()) return S;
                     hmac_midstates(key, K.inner, K.outer);
@@ -2263,11 +2328,17 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
                             k.limbs = (uint32_t)K.n.size(); k.limb_off = (uint32_t)jwk_limbs.size();
                             jwk_limbs.insert(jwk_limbs.end(), K.n.begin(), K.n.end());
                             jwk_limbs.insert(jwk_limbs.end(), K.rr.begin(), K.rr.end());
+                        } else if (!K.ec.empty()) {   // a P-256 key: its table, there too (960 bytes keep the boundary)
+                            k.limbs = JWT_EC_LIMBS; k.limb_off = (uint32_t)jwk_limbs.size();
+                            jwk_limbs.insert(jwk_limbs.end(), K.ec.begin(), K.ec.end());
                         }
                         djwk.push_back(k);
                     }
                 da.first_key = ins.first->second; da.n_keys = (uint32_t)set.keys.size();
-                for (uint32_t k = 0; k < da.n_keys; k++) if (djwk[da.first_key + k].limbs) da.rsa_mask |= 1u << k;
+                for (uint32_t k = 0; k < da.n_keys; k++) {
+                    const uint32_t kl = djwk[da.first_key + k].limbs;
+                    if (kl == JWT_EC_LIMBS) da.ec_mask |= 1u << k; else if (kl) da.rsa_mask |= 1u << k;
+                }
                 std::string nm;
                 Builder::auth_token_src(L.auth.token, da.src, nm);
                 da.name_off = C.put_bytes(nm); da.name_len = (uint32_t)nm.size();
@@ -2942,7 +3013,10 @@ CompileResult compile_generation(const uint8_t *blob, size_t len, uint32_t gen) 
     h.off_acc_rules = I.put(acc_rules); h.off_acc_lists = I.put(acc_lists);
     h.n_auth = (uint32_t)dauth.size(); h.n_jwks = (uint32_t)djwk.size();
     h.off_auth = I.put(dauth); h.off_jwks = I.put(djwk);
-    for (const DJwk &k : djwk) if (k.limbs) h.jwt_rsa_classes |= 1u << (k.limbs == JWT_RSA_K0 ? 0 : k.limbs == JWT_RSA_K1 ? 1 : 2);
+    for (const DJwk &k : djwk) {
+        if (k.limbs == JWT_EC_LIMBS) h.jwt_ec = 1;
+        else if (k.limbs) h.jwt_rsa_classes |= 1u << (k.limbs == JWT_RSA_K0 ? 0 : k.limbs == JWT_RSA_K1 ? 1 : 2);
+    }
     h.off_jwk_limbs = I.put(jwk_limbs);
     h.n_rk_cap = rkcap; h.n_rk_ids = (uint32_t)rk_ids.size(); h.n_rk_ents_keys = (uint32_t)rk_lists.size();
     h.off_rk = I.put(rk); h.off_rk_ids = I.put(rk_ids); h.off_rk_ents = I.put(rk_ents); h.off_rk_bloom = I.put(rk_bloom);

@@ -34,6 +34,7 @@
 #include "../../include/gpumatch.h"
 #include "gm_compile.hpp"
 #include "gm_inet.hpp"
+#include "gm_p256.hpp"
 #include "gm_tables.hpp"
 
 using namespace gm;
@@ -4225,7 +4226,9 @@ extern "C" int gm_auth_jwt(gm_ctx *c, const gm_batch *in, const gm_verdict *verd
     if ((e = grow(c, s, S->d_jit0, S->cap_jit0, (size_t)n)) || (e = grow(c, s, S->d_jit1, S->cap_jit1, (size_t)n)) ||
         (e = grow(c, s, S->d_jsig, S->cap_jsig, 8 * (size_t)n)) || (e = grow(c, s, S->d_jord, S->cap_jord, (size_t)n)) ||
         (e = grow(c, s, S->d_jctl, S->cap_jctl, (size_t)JWT_CTL_WORDS)) ||
-        (e = grow(c, s, S->d_jrsa, S->cap_jrsa, g->hdr.jwt_rsa_classes ? 3 * (size_t)n : 1)))
+        // (k_jwt_hmac lists class c at d_jrsa + c n: classes 0 .. 2 are RS256's, class 3 is ES256's, which
+        // k_jwt_find gives only under a DAuth.ec_mask -- and a set with an EC key sets hdr.jwt_ec)
+        (e = grow(c, s, S->d_jrsa, S->cap_jrsa, g->hdr.jwt_ec ? 4 * (size_t)n : g->hdr.jwt_rsa_classes ? 3 * (size_t)n : 1)))
         return e;
     const uint32_t blocks = (n + 255) / 256, sblocks = std::min<uint32_t>(blocks, (uint32_t)c->cu_count * 8);
     const long long now_s = (long long)std::min<uint64_t>(now, 1ull << 62);
@@ -4242,6 +4245,8 @@ extern "C" int gm_auth_jwt(gm_ctx *c, const gm_batch *in, const gm_verdict *verd
     if (rcls & 1) k_jwt_rsa<JWT_RSA_K0, true><<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, 0, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
     if (rcls & 2) k_jwt_rsa<JWT_RSA_K1, false><<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, 1, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
     if (rcls & 4) k_jwt_rsa<JWT_RSA_K2, false><<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, 2, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
+    // ES256: the fourth list, only where the generation has a P-256 key
+    if (g->hdr.jwt_ec) k_jwt_ec<<<rblocks, 64, 0, s>>>(in->arena, S->d_jctl, S->d_jrsa, S->d_jit0, S->d_jit1, S->d_jsig, g->jwt, n, out_auth);
     k_jwt_claims<<<blocks, 256, 0, s>>>(in->arena, S->d_jctl, S->d_jord, S->d_jit0, S->d_jit1, n, now_s, out_auth);
     HIPCHK(c, hipGetLastError());
     return G.done(c);

@@ -1,4 +1,4 @@
-// gm_jwt.inc -- HS256 and RS256 JWT verification for `auth_jwt` locations (NGINX Plus; nginx-plus.ingress.tmpl
+// gm_jwt.inc -- HS256, RS256 and ES256 JWT verification for `auth_jwt` locations (NGINX Plus; nginx-plus.ingress.tmpl
 // :105-111,186-188,223-228), included into gm_device.hip's anonymous namespace: gm_auth_jwt's kernels.
 //
 // THE GRAMMAR (include/gpumatch.h states the same; tests/jwt_reference.py restates it in Python).
@@ -11,11 +11,12 @@
 //   variables read them.  The token is the value's bytes up to its first space or its end; none, or
 //   an empty one: DENY / NO_TOKEN.  It must be exactly three non-empty segments of [A-Za-z0-9_-]
 //   split by two '.', with no padding; segment 3 is 43 characters (32 bytes) -- or, where the
-//   location's key set holds an RSA key, 342, 512 or 683 (256, 384, 512 bytes); a segment of 4k + 1
+//   location's key set holds an RSA key, 342, 512 or 683 (256, 384, 512 bytes), or, where it holds an EC
+//   key, 86 (r | s, 64 bytes); a segment of 4k + 1
 //   characters decodes to nothing.  Anything else: DENY / MALFORMED.
 // Header and payload.  Each decodes as base64url to one JSON object (whitespace around it allowed,
 //   nothing else).  Only top-level members are read, the last of a repeated name winning:
-//     alg   a string: "HS256" goes on, and "RS256" where the set holds an RSA key; "none" is DENY /
+//     alg   a string: "HS256" goes on, "RS256" where the set holds an RSA key, "ES256" where it holds an EC key; "none" is DENY /
 //           ALG_NONE, any other value (one written with an escape included) DEFER / ALG; missing or
 //           not a string: MALFORMED.
 //     kid   a string, optional (anything else there is ignored).
@@ -24,17 +25,22 @@
 //   Every other value is skipped: strings with their escapes honoured, objects and arrays by depth.
 //   A member name that holds a backslash is MALFORMED (deviation: nginx would unescape it; failing
 //   closed keeps an escaped "exp" from going unread).
-// Candidate keys.  The set's keys of the alg's kind -- `oct` for HS256, RSA for RS256; an RSA key is
-//   never an HMAC key -- whose kid equals the token's, byte for byte, if the token has a kid and some
+// Candidate keys.  The set's keys of the alg's kind -- `oct` for HS256, RSA for RS256, EC (P-256) for ES256; an
+//   RSA or EC key is never an HMAC key -- whose kid equals the token's, byte for byte, if the token has a kid and some
 //   key of that kind has that one; otherwise all keys of the kind (at most GM_JWT_KEYS in a set, of
-//   both kinds together).  None of the kind: DENY / SIGNATURE.
+//   all kinds together).  None of the kind: DENY / SIGNATURE.
 // Accept.  Some candidate key verifies (else DENY / SIGNATURE).  HS256: segment 3 is 43 characters
 //   (else MALFORMED) and HMAC-SHA-256(key, segment1 "." segment2 as sent) equals its 32 bytes.
 //   RS256, a key whose modulus n is k bytes (256, 384, 512; e = 65537): segment 3 is ceil(4k / 3)
 //   characters; its first 8k bits, a big-endian integer s, are < n (surplus bits ignored, as for
 //   HS256); and s^65537 mod n equals, over all k bytes, the EMSA-PKCS1-v1_5 encoding
 //   00 01 FF..FF 00 | 30 31 30 0d 06 09 60 86 48 01 65 03 04 02 01 05 00 04 20 | SHA-256(segment1 "."
-//   segment2) -- nothing inside the padding is parsed.  Then exp + leeway > now (else DENY / EXPIRED)
+//   segment2) -- nothing inside the padding is parsed.
+//   ES256 (group order n): segment 3 is 86 characters (HS256 with 86: MALFORMED; ES256 with another admitted
+//   length, RS256 with 86: SIGNATURE); its first 512 bits are r | s, big-endian, 1 <= r, s < n (the 4 surplus
+//   bits ignored); e = SHA-256(segment1 "." segment2), w = 1 / s, u1 = e w, u2 = r w (mod n), R = u1 G + u2 Q:
+//   R is not the point at infinity and x_R mod n = r.  High s is accepted.  A set without an EC key answers
+//   every input as before ES256 was known.  Then exp + leeway > now (else DENY / EXPIRED)
 //   and nbf <= now + leeway (else DENY / NOT_YET).  Claims are read only of a token whose signature
 //   verified, so a forged token is always SIGNATURE, whatever its payload.
 //
@@ -76,6 +82,17 @@
 //   token's own characters (the last characters are limb 0) straight into LDS, and checked < n on the
 //   way; for the last product it is decoded again (a = s, b = y: LDS held y by then).  The compare
 //   ORs the XORs of all K limbs against the encoding built from the digest: no early exit.
+// k_jwt_ec    ES256's hot path, one launch where the generation has a P-256 key, over the fourth list (an ES256
+//   token hashes like an RS256 one and lists itself as class 3): a lane per token, 64-thread groups, the whole
+//   verification in VGPRs and no LDS (gm_p256.hpp).  Field elements are eight 32-bit limbs in Montgomery form;
+//   p = -1 mod 2^32 makes the reduction of a row three adds and a subtract of the low limb, so a field product
+//   is 64 v_mad_u64_u32 and carry chains.  1 / s mod n is a fixed chain over generic 8-limb CIOS products.
+//   u1 G + u2 Q is Shamir's trick over joint 2-bit windows: 128 steps of two Jacobian doublings (a = -3) and
+//   one mixed addition of the key's table entry i G + j Q (the compiler wrote all 15, affine, Montgomery form:
+//   four dwordx4 loads through the key pointer), a (0, 0) window dropped by select.  The addition handles an
+//   accumulator at infinity (select), an addend equal to it (a doubling, under a branch) and opposite to it
+//   (Z = 0 falls out of the formula); Z = 0 at the end is refused before the compare r Z^2 = X or (r + n) Z^2
+//   = X, which needs no inversion and ORs the XORs of all limbs.
 // k_jwt_claims a lane per verified token, in the same order: exp / nbf from the payload through the
 //   streaming reader, then out_auth.
 
@@ -86,7 +103,8 @@ constexpr uint32_t JWT_CTL_HIST = 2, JWT_CTL_CUR = JWT_CTL_HIST + JWT_BINS, JWT_
                    JWT_CTL_WORDS = JWT_CTL_RSA + 4;
 // item0.x: the SHA block count, and above it
 constexpr uint32_t JWT_VERIFIED = 0x80000000u;   // k_jwt_hmac / k_jwt_rsa verified the signature
-constexpr uint32_t JWT_RSA = 0x40000000u;        // an RS256 token, its modulus size class (0 .. 2) at JWT_CLS_SHIFT
+constexpr uint32_t JWT_RSA = 0x40000000u;        // an RS256 token, its modulus size class (0 .. 2) at JWT_CLS_SHIFT,
+constexpr uint32_t JWT_CLS_EC = 3;               // or an ES256 token: class 3 (both hash as plain SHA-256)
 constexpr uint32_t JWT_CLS_SHIFT = 28, JWT_NB_MASK = (1u << JWT_CLS_SHIFT) - 1;
 
 struct JwtTab {
@@ -94,7 +112,7 @@ struct JwtTab {
     const DJwk *keys;
     const uint8_t *bytes;
     uint32_t n_locs, gen;
-    const uint32_t *limbs;   // the RSA keys' n and RR (DJwk.limb_off)
+    const uint32_t *limbs;   // the RSA keys' n and RR, the EC keys' tables (DJwk.limb_off)
 };
 
 __device__ __forceinline__ uint32_t jwt_code(uint32_t code, uint32_t reason) { return code | reason << 8; }
@@ -127,7 +145,7 @@ struct JwtRd {
     }
 };
 
-enum : uint32_t { JALG_MISSING, JALG_HS256, JALG_NONE, JALG_OTHER, JALG_BAD, JALG_RS256 };
+enum : uint32_t { JALG_MISSING, JALG_HS256, JALG_NONE, JALG_OTHER, JALG_BAD, JALG_RS256, JALG_ES256 };
 struct JwtDoc {
     uint32_t alg, kid_mask;
     bool has_kid, has_exp, has_nbf;
@@ -213,6 +231,7 @@ __device__ bool jwt_alg(JwtRd &r, uint32_t &alg) {
         if (l < 4) v0 |= (uint32_t)c << (8 * l); else if (l < 8) v1 |= (uint32_t)c << (8 * (l - 4));
     }
     alg = esc ? JALG_OTHER : l == 5 && v0 == 0x35325348u && v1 == '6' ? JALG_HS256 : l == 5 && v0 == 0x35325352u && v1 == '6' ? JALG_RS256 :
+          l == 5 && v0 == 0x35325345u && v1 == '6' ? JALG_ES256 :
           l == 4 && v0 == 0x656E6F6Eu ? JALG_NONE : JALG_OTHER;
     return true;
 }
@@ -319,7 +338,8 @@ __device__ uint32_t jwt_find(const uint8_t *A, uint64_t len, const gm_req *rp, c
         } else if (!jwt_b64ok(c)) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
     }
     const uint32_t sl = tl - d2 - 1;   // segment 3 (if there is one)
-    const bool sl_ok = sl == 43 || (a.rsa_mask && (sl == jwt_rsa_chars(JWT_RSA_K0) || sl == jwt_rsa_chars(JWT_RSA_K1) || sl == jwt_rsa_chars(JWT_RSA_K2)));
+    const bool sl_ok = sl == 43 || (a.rsa_mask && (sl == jwt_rsa_chars(JWT_RSA_K0) || sl == jwt_rsa_chars(JWT_RSA_K1) || sl == jwt_rsa_chars(JWT_RSA_K2))) ||
+                       (a.ec_mask && sl == JWT_EC_CHARS);
     if (d2 == GM_NONE || d1 == 0 || d2 == d1 + 1 || !sl_ok || (d1 & 3) == 1 || ((d2 - d1 - 1) & 3) == 1)
         return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
     JwtRd rd;
@@ -328,7 +348,17 @@ __device__ uint32_t jwt_find(const uint8_t *A, uint64_t len, const gm_req *rp, c
     if (!jwt_walk(rd, true, t, a, d) || d.alg == JALG_MISSING || d.alg == JALG_BAD) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
     if (d.alg == JALG_NONE) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_ALG_NONE);
     const uint32_t slen = d2, all = (1u << a.n_keys) - 1;   // slen: segment1 "." segment2
+    if (d.alg == JALG_ES256 && a.ec_mask) {
+        // the EC keys, narrowed by kid; r | s stay in the text
+        if (sl != JWT_EC_CHARS) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
+        uint32_t cand = all & a.ec_mask;
+        if (d.has_kid && (d.kid_mask & cand)) cand &= d.kid_mask;
+        it0 = make_uint4((slen + 9 + 63) / 64 | JWT_RSA | JWT_CLS_EC << JWT_CLS_SHIFT, slen, (uint32_t)vo, (uint32_t)(vo >> 32));
+        it1 = make_uint4(a.first_key, cand, d1 + 1, a.leeway);
+        return GM_NONE;
+    }
     if (d.alg == JALG_RS256 && a.rsa_mask) {
+        if (sl == JWT_EC_CHARS) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);   // (no RSA key of that size)
         // the RSA keys, narrowed by kid, that are of the size segment 3 has; the signature stays in the text
         uint32_t cand = all & a.rsa_mask, fit = 0;
         if (d.has_kid && (d.kid_mask & cand)) cand &= d.kid_mask;
@@ -342,7 +372,7 @@ __device__ uint32_t jwt_find(const uint8_t *A, uint64_t len, const gm_req *rp, c
     }
     if (d.alg != JALG_HS256) return jwt_code(GM_AUTH_DEFER, GM_AUTH_R_ALG);
     if (sl != 43) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_MALFORMED);
-    uint32_t cand = all & ~a.rsa_mask;
+    uint32_t cand = all & ~a.rsa_mask & ~a.ec_mask;
     if (!cand) return jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
     if (d.has_kid && (d.kid_mask & cand)) cand &= d.kid_mask;
     // segment 3: 43 characters = 258 bits, the first 256 of them as eight big-endian words
@@ -438,7 +468,7 @@ __global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A,
     const uint32_t i = min(order[gid], n - 1);
     const uint4 it0 = item0[i], it1 = item1[i];
     const uint32_t nb = it0.x & JWT_NB_MASK, len = it0.y;
-    const bool rsa = it0.x & JWT_RSA;   // plain SHA-256 of the signing input: the digest is k_jwt_rsa's
+    const bool rsa = it0.x & JWT_RSA;   // plain SHA-256 of the signing input: the digest is k_jwt_rsa's or k_jwt_ec's
     const uint32_t bits = ((rsa ? 0u : 64u) + len) * 8u;   // (an HMAC's key block came first)
     const uint64_t text = (uint64_t)it0.z | (uint64_t)it0.w << 32;
     const uint32_t s = (uint32_t)text & 3u, sel = 0x00010203u + 0x01010101u * s;
@@ -506,7 +536,7 @@ __global__ __launch_bounds__(256) void k_jwt_hmac(const uint8_t *__restrict__ A,
     }
     const uint32_t cls = it0.x >> JWT_CLS_SHIFT & 3u;
     const uint32_t pos = jwt_bin_add(ctl + JWT_CTL_RSA, cls, rsa);
-    if (rsa) rlist[(size_t)min(cls, 2u) * n + min(pos, n - 1)] = i;
+    if (rsa) rlist[(size_t)cls * n + min(pos, n - 1)] = i;   // (class 3 only where the generation has an EC key: 4 n words)
     else if (ok) item0[i].x = nb | JWT_VERIFIED;
     else out_auth[i] = jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
 }
@@ -629,6 +659,43 @@ __global__ __launch_bounds__(64) void k_jwt_rsa(const uint8_t *__restrict__ A, c
 #pragma unroll
         for (uint32_t j = 0; j < K; j++) diff |= b[j] ^ jwt_rsa_em<K>(d, j);
         ok = diff == 0;
+    }
+    if (ok) item0[i].x = it0.x | JWT_VERIFIED;
+    else out_auth[i] = jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);
+}
+
+// ES256's hot path: a lane per token of the fourth list, 64-thread groups.  The whole verification lives in the
+// lane's VGPRs (gm_p256.hpp: ecdsa_verify) -- no LDS; the key's table is read through the key pointer, four
+// dwordx4 loads a ladder step (the lanes of a wave nearly always share the key: at most 15 distinct 64-byte
+// entries).  r | s are decoded from the token's own characters: limb j of the 512-bit integer is stream bits
+// [32 (15 - j), 32 (16 - j)), at most seven characters, all of them the segment's 86.
+__global__ __launch_bounds__(64) void k_jwt_ec(const uint8_t *__restrict__ A, const uint32_t *__restrict__ ctl,
+                                               const uint32_t *__restrict__ rlist, uint4 *__restrict__ item0,
+                                               const uint4 *__restrict__ item1, const uint32_t *__restrict__ dig, JwtTab t,
+                                               uint32_t n, uint32_t *__restrict__ out_auth) {
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+    if (gid >= min(ctl[JWT_CTL_RSA + JWT_CLS_EC], n)) return;
+    const uint32_t i = min(rlist[(size_t)JWT_CLS_EC * n + gid], n - 1);
+    const uint4 it0 = item0[i], it1 = item1[i];
+    const uint8_t *S = A + ((uint64_t)it0.z | (uint64_t)it0.w << 32) + it0.y + 1;   // segment 3
+    p256::Fe e, r, s;
+    {
+        const uint4 p = reinterpret_cast<const uint4 *>(dig + 8 * (size_t)i)[0], q = reinterpret_cast<const uint4 *>(dig + 8 * (size_t)i)[1];
+        e.v[7] = p.x; e.v[6] = p.y; e.v[5] = p.z; e.v[4] = p.w; e.v[3] = q.x; e.v[2] = q.y; e.v[1] = q.z; e.v[0] = q.w;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 16; j++) {
+        const uint32_t lo = 32 * (15 - j), c1 = (lo + 31) / 6;
+        unsigned long long acc = 0;
+#pragma unroll
+        for (uint32_t c = lo / 6; c <= c1; c++) acc = acc << 6 | jwt_b64v(S[c]);
+        const uint32_t v = (uint32_t)(acc >> (6 * (c1 + 1) - (lo + 32)));
+        if (j < 8) s.v[j] = v; else r.v[j - 8] = v;
+    }
+    bool ok = false;
+    for (uint32_t m = it1.y & ((1u << JWT_KEYS_MAX) - 1); m && !ok; m &= m - 1) {   // (only a lane that failed goes round again)
+        const DJwk *J = t.keys + it1.x + (uint32_t)__builtin_ctz(m);   // (an EC key: k_jwt_find masked with ec_mask)
+        ok = p256::ecdsa_verify(e, r, s, t.limbs + J->limb_off);
     }
     if (ok) item0[i].x = it0.x | JWT_VERIFIED;
     else out_auth[i] = jwt_code(GM_AUTH_DENY, GM_AUTH_R_SIGNATURE);

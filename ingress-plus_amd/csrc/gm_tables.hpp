@@ -174,7 +174,8 @@ struct DAuth {
     uint32_t realm_off, realm_len;
     uint32_t login_loc;      // the `error_page 401` named location (jwt-login-url), GM_NONE: none
     uint32_t rsa_mask;       // bit k: the set's key k is an RSA key (0: an oct-only set, the HS256 grammar alone)
-    uint32_t pad[2];
+    uint32_t ec_mask;        // bit k: the set's key k is a P-256 key (0: ES256 stays another alg, 86 characters no shape)
+    uint32_t pad;
 };
 // One `oct` key of a JWK set: HMAC-SHA-256's two midstates -- the SHA-256 state after the one block
 // K' ^ ipad and after K' ^ opad (K': the key zero-padded to 64 bytes, a longer key hashed first,
@@ -182,11 +183,15 @@ struct DAuth {
 // An RSA public key (e = 65537) instead: limbs = K, the modulus's 32-bit limbs (JWT_RSA_K0/1/2: 2048,
 // 3072 or 4096 bits); limb_off is the word offset, in the image's limb section (16-byte aligned), of
 // n[K] followed by RR[K] = 2^(64 K) mod n, least significant limb first; inner[0] = -1/n mod 2^32.
+// A P-256 public key Q instead: limbs = JWT_EC_LIMBS, and limb_off is the word offset in the same section of
+// the key's table (gm_p256.hpp): 15 affine points i G + j Q, i, j in 0 .. 3 not both 0, entry 4 i + j - 1, each
+// x then y as eight limbs in Montgomery form mod p -- 960 bytes; inner and outer are zero.
 struct DJwk {
     uint32_t inner[8], outer[8];
     uint32_t kid_off, kid_len;     // the key's kid (bytes pool; kid_len 0: none)
     uint32_t limbs, limb_off;      // limbs 0: an `oct` key
 };
+constexpr uint32_t JWT_EC_LIMBS = 8, JWT_EC_CHARS = 86;   // a field element's limbs; r | s, 64 bytes, in base64url
 constexpr uint32_t JWT_RSA_K0 = 64, JWT_RSA_K1 = 96, JWT_RSA_K2 = 128;
 __host__ __device__ constexpr uint32_t jwt_rsa_k(uint32_t cls) { return cls == 0 ? JWT_RSA_K0 : cls == 1 ? JWT_RSA_K1 : JWT_RSA_K2; }
 // the base64url characters of a K-limb signature: ceil(4 k / 3) for k = 4 K bytes (342, 512, 683)
@@ -472,8 +477,9 @@ struct TabHeader {
     uint64_t off_acc_rules, off_acc_lists;
     uint32_t n_auth, n_jwks;             // DAuth records (0 or n_locs) and the DJwk keys of every set
     uint64_t off_auth, off_jwks;
-    uint32_t jwt_rsa_classes, pad_rsa;   // bit c: some RSA key has jwt_rsa_k(c) limbs (the k_jwt_rsa launches needed)
-    uint64_t off_jwk_limbs;              // u32: the RSA keys' n and RR (DJwk.limb_off)
+    uint32_t jwt_rsa_classes, jwt_ec;    // bit c: some RSA key has jwt_rsa_k(c) limbs (the k_jwt_rsa launches needed);
+                                         // jwt_ec: some key is a P-256 key (the k_jwt_ec launch needed)
+    uint64_t off_jwk_limbs;              // u32: the RSA keys' n and RR, the EC keys' tables (DJwk.limb_off)
 };
 // The route's hot tables -- ports, the three name tables, servers, server ifs, small-location
 // lists, locations and the name strings -- are laid out first and contiguously in the image;

@@ -23,7 +23,8 @@ def make_blob(main: str | bytes | None, confd: dict, sigs_text: str | bytes | No
     """``sample``: optional benign traffic bytes (GM_ENTRY_SAMPLE) -- the compiler uses them only to
     choose the WAF prefilter's key windows and hash multiplier; matching results never depend
     on it.  ``jwks``: JWT key files (GM_ENTRY_JWK), path as ``auth_jwt_key_file`` writes it -> the
-    file's bytes (a JWK set of `oct` keys and RSA public keys of 2048, 3072 or 4096 bits, e = 65537);
+    file's bytes (a JWK set of `oct` keys and RSA public keys of 2048, 3072 or 4096 bits, e = 65537, and
+    P-256 public keys ``{"kty": "EC", "crv": "P-256", "x", "y"}``);
     supplying one promises that ``Engine.auth_jwt`` runs on the verdicts."""
     entries = []
     if main is not None:

@@ -13,8 +13,13 @@ cycled over the batch (a tenth of them forged), verified by k_jwt_rsa (a lane pe
 products); outcomes are compared with tests/jwt_rsa_reference.py on the distinct tokens, the same
 batch saying RS384 gives the find + order share, and the restatement's own pow() is timed as context.
 
+`--alg ES256` is the ECDSA leg: the P-256 key of tests/golden/jwt/ec-p256, 512 distinct tokens (a tenth forged),
+verified by k_jwt_ec (a lane per token; gm_p256.hpp); outcomes are compared with tests/jwt_ec_reference.py, the
+same batch saying ES384 gives the find + order share.
+
     python scripts/bench_jwt.py [--n 1000000] [--reps 10] [--warmup 3] [--large 0.1]
     python scripts/bench_jwt.py --alg RS256 [--n 65536]
+    python scripts/bench_jwt.py --alg ES256 [--n 65536]
 """
 
 import argparse
@@ -31,6 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ingress-plus_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import jwt_ec_reference as ec  # noqa: E402
 import jwt_reference as ref  # noqa: E402
 import jwt_rsa_reference as rsa  # noqa: E402
 from gpumatch import blob, engine, records  # noqa: E402
@@ -115,9 +121,35 @@ def rsa_leg(a, e, dev):
                       "python_restatement_tokens_per_s_one_thread": round(1 / cpu_s), "csrc_hash": engine.build_hash()}))
 
 
+def ec_leg(a, e, dev):
+    n = a.n if a.n != 1_000_000 else 65536
+    d, q = ec.fixture_key()
+    pub = ec.jwk(q, "0001")
+    e.load(blob.make_blob(None, {"c": CONF}, jwks={"/k": json.dumps({"keys": [pub]})}), 1)
+    res = {}
+    for alg in ("ES256", "ES384"):
+        toks = [ec.sign(d, {"typ": "JWT", "alg": alg, "kid": "0001"}, {"sub": "q%05x" % i, "iss": "My API Gateway"}) for i in range(512)]
+        toks = [t[:-2] + ("A" if t[-2] != "A" else "B") + t[-1] if i % 10 == 9 else t for i, t in enumerate(toks)]   # (a tenth forged)
+        ms, got = timed(e, a, dev, toks, n)
+        t0 = time.perf_counter()
+        want = np.array([ec.outcome(t, [("0001", q)], NOW) for t in toks], dtype=np.uint32)
+        cpu_s = (time.perf_counter() - t0) / len(toks)
+        assert np.array_equal(got, want[np.arange(n) % len(toks)]), alg
+        res[alg] = (float(np.median(ms)), ms, cpu_s)
+    med, ms, cpu_s = res["ES256"]
+    ec_ms = med - res["ES384"][0]
+    # per token: 128 x (2 doublings of 8 + a mixed addition of 11) + 5 field products, about 330 scalar products
+    print(json.dumps({"bench": "jwt_es256", "n": n, "curve": "P-256", "distinct_tokens": 512, "ms_median": round(med, 4),
+                      "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "reps": a.reps, "tokens_per_s": round(n / med * 1e3),
+                      "ms_find_order_median": round(res["ES384"][0], 4), "ms_hash_ec_claims_by_difference": round(ec_ms, 4),
+                      "field_products_per_s": round((128 * 27 + 5) * n / ec_ms * 1e3),
+                      "multiply_adds_per_s": round(((128 * 27 + 5) * 64 + 330 * 128) * n / ec_ms * 1e3),
+                      "python_restatement_tokens_per_s_one_thread": round(1 / cpu_s), "csrc_hash": engine.build_hash()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", choices=["HS256", "RS256"], default="HS256")
+    ap.add_argument("--alg", choices=["HS256", "RS256", "ES256"], default="HS256")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -129,6 +161,8 @@ def main():
     e = engine.Engine(0)
     if a.alg == "RS256":
         return rsa_leg(a, e, dev)
+    if a.alg == "ES256":
+        return ec_leg(a, e, dev)
     e.load(blob.make_blob(None, {"c": CONF}, jwks={"/k": json.dumps({"keys": [{"kty": "oct", "k": ref.b64e(KEY), "kid": "0001"}]})}), 1)
     assert e.stats()["n_auth_locations"] == 1
     ver = np.zeros(a.n, dtype=records.VERDICT_DTYPE)
