@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GM_ABI_VERSION 14u  /* 14: gm_auth_jwt, gm_auth_info, GM_ENTRY_JWK, gm_stats_t.n_auth_locations (appended); 13: gm_xml_bodies, GM_DEC_XML, gm_stats_t.last_xml (was reserved1); 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
+#define GM_ABI_VERSION 15u  /* 15: gm_ws_messages, gm_ws_seg, gm_ws_result; 14: gm_auth_jwt, gm_auth_info, GM_ENTRY_JWK, gm_stats_t.n_auth_locations (appended); 13: gm_xml_bodies, GM_DEC_XML, gm_stats_t.last_xml (was reserved1); 12: gm_multipart_bodies, GM_DEC_MULTIPART, gm_stats_t.last_multipart; 11: gm_inflate_bodies, GM_DEC_GZIP, gm_stats_t.last_inflated; 10: gm_sync_batches, GM_E_EARLIER; 9: gm_stats_t.csrc_hash, gm_build_hash, GM_ACT_FORBIDDEN, GM_ROUTE_HELD; 8: PROXY protocol (gm_wire_msg 128 B, $proxy_protocol_addr in gm_req), last_redo;
                                7: GM_ACT_TOO_LARGE, GM_REQ_CHUNKED, gm_rejects, build flags; 6: n_rsl_reversed;
                                5: gm_update_upstream / gm_peers_migrate; 4: union-DFA stats */
 
@@ -53,7 +53,7 @@ extern "C" {
                                 batch that sync completed is void: any other outcome of the forced
                                 sync comes back as gm_sync reports it (GM_E_OVERFLOW for a
                                 gm_parse_requests / gm_upstream_uris / gm_inflate_bodies /
-                                gm_multipart_bodies / gm_xml_bodies capacity overflow: every batch is whole, and
+                                gm_multipart_bodies / gm_xml_bodies / gm_ws_messages capacity overflow: every batch is whole, and
                                 this one was not enqueued either) */
 
 /* ---------------------------------------------------------------- gm_create flags */
@@ -370,7 +370,7 @@ int         gm_sync(gm_ctx *ctx, void *stream);
  * gm_sync / gm_sync_batches on the stream, forced completions included, in enqueue order; it
  * returns that number of batches (entries past `cap` are not written), or a negative GM_E_* for an
  * error no batch status describes (HIP; gm_parse_requests / gm_upstream_uris / gm_inflate_bodies /
- * gm_multipart_bodies / gm_xml_bodies capacity, which gm_sync reports the same way, once: the sync that reports it
+ * gm_multipart_bodies / gm_xml_bodies / gm_ws_messages capacity, which gm_sync reports the same way, once: the sync that reports it
  * clears it; the statuses are then kept for the next call).  gm_sync discards them. */
 int         gm_sync_batches(gm_ctx *ctx, void *stream, int32_t *status, size_t cap);
 
@@ -558,6 +558,63 @@ int         gm_multipart_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, u
  * gm_sync.  Needs no generation: the kernel gm_match_batch runs for a signature set that declares `xml`. */
 int         gm_xml_bodies(gm_ctx *ctx, const gm_batch *in, uint8_t *out, uint64_t out_cap,
                           uint64_t *out_off, uint32_t *out_len, void *stream);
+
+/* ---------------------------------------------------------------- WebSocket frames
+ * (`wallarm_parse_websocket`: after the 101 the client's bytes are RFC 6455 frames -- masked, fragmented,
+ * behind 2 / 4 / 10-byte length headers.)  The unmasked message view V of every segment, a wave per
+ * segment (gm_ws.inc states the same grammar beside the kernel).
+ *  - A segment is a run of one connection's client-to-server bytes, wire[off, off + len).  It begins
+ *    at a frame boundary with no message open.  Frames are read left to right.
+ *  - Header: byte 0 is FIN | RSV1-3 | opcode, byte 1 is MASK | len7; len7 == 126 is followed by a
+ *    16-bit, len7 == 127 by a 64-bit big-endian length; the 4-byte masking key follows the length;
+ *    payload byte k is wire ^ key[k & 3].
+ *  - Protocol errors stop the segment with GM_WS_PROTO and a reason.  The first two bytes are judged
+ *    as soon as both are there; the first reason that applies, in this order, is reported:
+ *      RSV        RSV2 or RSV3 set, or RSV1 set on a control or continuation frame
+ *      OPCODE     opcode 3-7 or 0xB-0xF
+ *      UNMASKED   MASK = 0
+ *      CTRL_FRAG  a control frame with FIN = 0
+ *      CTRL_LEN   a control frame with len7 > 125
+ *      CONT       opcode 0 with no message open
+ *      NESTED     opcode 1 or 2 while a message is open
+ *      LENGTH     (once the length's bytes are there) a 16-bit form holding a value < 126, a 64-bit
+ *                 form holding a value < 65536, or the 64-bit form's top bit set
+ *  - RSV1 on an opcode-1 or opcode-2 frame that passes the checks above (permessage-deflate) stops
+ *    before that frame with GM_WS_DEFLATE: it is not inflated.
+ *  - A frame whose header or payload runs past the segment's end stops with GM_WS_OK: not an error.
+ *  - A complete close frame (opcode 8) stops with GM_WS_CLOSED, consumed = the offset after it.
+ *  - Ping and pong payloads are not emitted.
+ *  - V: for every complete data message in order -- an opcode-1 or -2 frame, then continuation frames,
+ *    up to FIN = 1, control frames allowed in between -- its fragments' unmasked payloads joined,
+ *    then '\n'.  No UTF-8 validation.  A message still open at the stop contributes nothing (its
+ *    bytes may lie in the slot past out_len); n_messages counts the complete ones.
+ *  - stop = the offset of the frame at which reading stopped (len: the segment was read out).
+ *    consumed = the offset after the last frame behind which no message was open: the caller submits
+ *    the connection's bytes from there again, with what arrived since.
+ *  - |V| <= len (proof in gm_ws.inc): segment i's slot is len bytes.
+ * out_off[i] = the exclusive sum of len; out_len[i] = |V| of segment i at out[out_off[i]] (0 is a valid
+ * view); a segment past out_cap gets out_len[i] = GM_NONE and an all-zero result, and gm_sync then
+ * reports GM_E_OVERFLOW.  out_cap >= the sum of len always suffices.  Device pointers (segs 8-byte,
+ * res 16-byte aligned; every segment inside the caller's wire buffer), asynchronous on `stream`,
+ * completed by gm_sync; n == 0 is a no-op.  Needs no generation. */
+typedef struct gm_ws_seg { uint64_t off; uint32_t len; uint32_t pad; } gm_ws_seg;      /* 16 B */
+typedef struct gm_ws_result { uint32_t status;      /* GM_WS_* | reason << 8 */
+                              uint32_t consumed, stop, n_messages; } gm_ws_result;     /* 16 B */
+#define GM_WS_OK        0u
+#define GM_WS_CLOSED    1u
+#define GM_WS_DEFLATE   2u
+#define GM_WS_PROTO     3u
+#define GM_WS_R_RSV        1u
+#define GM_WS_R_OPCODE     2u
+#define GM_WS_R_UNMASKED   3u
+#define GM_WS_R_CTRL_FRAG  4u
+#define GM_WS_R_CTRL_LEN   5u
+#define GM_WS_R_LENGTH     6u
+#define GM_WS_R_CONT       7u
+#define GM_WS_R_NESTED     8u
+int         gm_ws_messages(gm_ctx *ctx, const uint8_t *wire, const gm_ws_seg *segs, uint32_t n,
+                           uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *out_len,
+                           gm_ws_result *res, void *stream);
 
 /* ---------------------------------------------------------------- auth_jwt (NGINX Plus)
  * HS256, RS256 and ES256 JWT verification for the locations `auth_jwt "<realm>" [token=$cookie_NAME | $arg_NAME |

@@ -1687,6 +1687,7 @@ __global__ __launch_bounds__(ROUTE_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE
 #include "gm_inflate.inc"
 #include "gm_multipart.inc"
 #include "gm_xml.inc"
+#include "gm_ws.inc"
 #include "gm_jwt.inc"
 
 }  // namespace
@@ -1802,6 +1803,10 @@ struct Scratch {
     uint64_t *d_xoff = nullptr; size_t cap_xoff = 0;
     uint32_t *d_xlen = nullptr; size_t cap_xlen = 0;
     uint8_t *d_xout = nullptr; size_t cap_xout = 0;
+    // gm_ws_messages (gm_ws.inc): slot sizes, scan temp, the queue head
+    uint64_t *d_wslim = nullptr; size_t cap_wslim = 0;
+    uint8_t *d_wstemp = nullptr; size_t cap_wstemp = 0;
+    uint32_t *d_wsctl = nullptr; size_t cap_wsctl = 0;
     // gm_auth_jwt (gm_jwt.inc): per request a work item (two uint4) and the signature's eight
     // words (an RS256 token's: its digest), the items' order by SHA block count, control words, and
     // the RS256 tokens listed by modulus size (three lists of n)
@@ -1868,7 +1873,7 @@ struct Scratch {
                         (void *)d_zlim, (void *)d_zlist, (void *)d_zctl, (void *)d_ztemp, (void *)d_zoff, (void *)d_zlen,
                         (void *)d_zout, (void *)d_mlim, (void *)d_mbnd, (void *)d_mlist, (void *)d_mctl, (void *)d_mtemp,
                         (void *)d_moff, (void *)d_mlen, (void *)d_mflg, (void *)d_mout, (void *)d_xlim, (void *)d_xlist, (void *)d_xctl,
-                        (void *)d_xtemp, (void *)d_xoff, (void *)d_xlen, (void *)d_xout,
+                        (void *)d_xtemp, (void *)d_xoff, (void *)d_xlen, (void *)d_xout, (void *)d_wslim, (void *)d_wstemp, (void *)d_wsctl,
                         (void *)d_jit0, (void *)d_jit1, (void *)d_jsig, (void *)d_jord, (void *)d_jctl, (void *)d_jrsa})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
@@ -3227,7 +3232,7 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     }
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
     const uint32_t infl_ov = S->h_status[INFL_STATUS_WORD], mp_ov = S->h_status[MP_STATUS_WORD];
-    const uint32_t xml_ov = S->h_status[XML_STATUS_WORD];
+    const uint32_t xml_ov = S->h_status[XML_STATUS_WORD], ws_ov = S->h_status[WS_STATUS_WORD];
     std::vector<Scratch::Replay> pend;
     pend.swap(S->pending);
     const bool last_in_place = S->last_is_batch;
@@ -3271,11 +3276,13 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
     if (infl_ov) HIPCHK(c, hipMemsetAsync(S->d_status + INFL_STATUS_WORD, 0, 4, S->stream));
     if (mp_ov) HIPCHK(c, hipMemsetAsync(S->d_status + MP_STATUS_WORD, 0, 4, S->stream));
     if (xml_ov) HIPCHK(c, hipMemsetAsync(S->d_status + XML_STATUS_WORD, 0, 4, S->stream));
+    if (ws_ov) HIPCHK(c, hipMemsetAsync(S->d_status + WS_STATUS_WORD, 0, 4, S->stream));
     if (parse_ov) return fail(c, GM_E_OVERFLOW, "gm_parse_requests: arena capacity exceeded");
     if (upuri_ov) return fail(c, GM_E_OVERFLOW, "gm_upstream_uris: output capacity exceeded");
     if (infl_ov) return fail(c, GM_E_OVERFLOW, "gm_inflate_bodies: output capacity exceeded");
     if (mp_ov) return fail(c, GM_E_OVERFLOW, "gm_multipart_bodies: output capacity exceeded");
     if (xml_ov) return fail(c, GM_E_OVERFLOW, "gm_xml_bodies: output capacity exceeded");
+    if (ws_ov) return fail(c, GM_E_OVERFLOW, "gm_ws_messages: output capacity exceeded");
     if (err & OV_HITS) return fail(c, GM_E_OVERFLOW, "hit_ids capacity exceeded (the batch's counters were not committed)");
     // candidate / survivor / pair / job overflows were completed on the device (k_waf_direct, the
     // set-based scatter and regex runs): the batch is whole, the buffers grow for speed
@@ -3288,7 +3295,8 @@ static int sync_pending(gm_ctx *c, Scratch *S) {
 // The sync a gm_match_batch forces on its stream: GM_E_EARLIER when one of the batches it completed
 // is void (a GM_E_OVERFLOW among the sync_log entries it added; gm_sync_batches names it).  Any
 // other outcome is returned as gm_sync reports it -- a gm_parse_requests / gm_upstream_uris /
-// gm_inflate_bodies / gm_multipart_bodies capacity overflow is GM_E_OVERFLOW with every batch whole.
+// gm_inflate_bodies / gm_multipart_bodies / gm_xml_bodies / gm_ws_messages capacity overflow is GM_E_OVERFLOW with
+// every batch whole.
 static int forced_sync(gm_ctx *c, Scratch *S, const char *where) {
     const size_t n0 = S->sync_log.size();
     const int e0 = sync_pending(c, S);
@@ -3388,7 +3396,7 @@ int gm_sync_batches(gm_ctx *c, void *stream, int32_t *status, size_t cap) {
     if (e && e != GM_E_OVERFLOW) return e;   // (a HIP error: the log stays for the next call)
     const uint32_t parse_ov = S->h_status[PARSE_STATUS_WORD + 3], upuri_ov = S->h_status[UPURI_STATUS_WORD];
     if (e && (parse_ov || upuri_ov || S->h_status[INFL_STATUS_WORD] || S->h_status[MP_STATUS_WORD] ||
-              S->h_status[XML_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
+              S->h_status[XML_STATUS_WORD] || S->h_status[WS_STATUS_WORD])) return e;   // not a gm_match_batch's: reported as gm_sync does
     const size_t n = S->sync_log.size();
     for (size_t i = 0; i < n && i < cap; i++) status[i] = S->sync_log[i];
     S->sync_log.clear();
@@ -4201,6 +4209,38 @@ extern "C" int gm_xml_bodies(gm_ctx *c, const gm_batch *in, uint8_t *out, uint64
     if (int e = launch_xml(c, S, in->reqs, in->arena, in->arena_len, in->arena_len_dev, n, nullptr, nullptr, out, out_cap,
                            out_off, out_len, nullptr, S->d_status + XML_STATUS_WORD))
         return e;
+    return G.done(c);
+}
+
+// ---------------------------------------------------------------- WebSocket frames (wallarm_parse_websocket)
+// Slot sizes (the segments' lengths), one exclusive scan, the persistent wave-per-segment kernel.
+extern "C" int gm_ws_messages(gm_ctx *c, const uint8_t *wire, const gm_ws_seg *segs, uint32_t n, uint8_t *out,
+                              uint64_t out_cap, uint64_t *out_off, uint32_t *out_len, gm_ws_result *res, void *stream) {
+    if (!c) return fail(c, GM_E_INVAL, "null argument");
+    if (c->flags & GM_CREATE_COMPILE_ONLY) return fail(c, GM_E_NODEVICE, "compile-only context");
+    if (n && (!wire || !segs || !out_off || !out_len || !res || (!out && out_cap))) return fail(c, GM_E_INVAL, "null argument");
+    if (((uintptr_t)segs & 7) || ((uintptr_t)res & 15)) return fail(c, GM_E_INVAL, "segs must be 8-byte, res 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t s = (hipStream_t)stream;
+    Scratch *S = scratch_for(c, s);
+    if (!S) return fail(c, GM_E_NOMEM, t_err);
+    DoneGuard G(S);
+    if (n == 0) return GM_OK;
+    HIPCHK(c, hipMemsetAsync(S->d_status + WS_STATUS_WORD, 0, 4, s));
+    int e;
+    if ((e = grow(c, s, S->d_wslim, S->cap_wslim, (size_t)n + 1))) return e;
+    if ((e = grow(c, s, S->d_wsctl, S->cap_wsctl, (size_t)1))) return e;
+    size_t tb = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, S->d_wslim, out_off, (int)n, s));
+    if ((e = grow(c, s, S->d_wstemp, S->cap_wstemp, tb))) return e;
+    const uint32_t sblocks = std::max<uint32_t>(1, std::min<uint32_t>((n + 255) / 256, (uint32_t)c->cu_count * 8));
+    k_ws_size<<<sblocks, 256, 0, s>>>(segs, n, S->d_wslim, S->d_wsctl);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_wstemp, tb, S->d_wslim, out_off, (int)n, s));
+    // 8 workgroups of 4 waves per CU: a wave's steps are dependent (the walk, the carried state), occupancy hides them
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n + WS_WAVES - 1) / WS_WAVES, (uint32_t)c->cu_count * 8));
+    k_ws<<<blocks, WS_BLOCK, 0, s>>>(wire, segs, n, S->d_wsctl, out, out_cap, out_off, out_len, res, S->d_status + WS_STATUS_WORD);
+    HIPCHK(c, hipGetLastError());
     return G.done(c);
 }
 

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GM_LIB") or os.path.join(os.path.dirname(HERE), "libgpumatch.so")
 
 GM_OK = 0
-GM_ABI_VERSION = 14  # include/gpumatch.h
+GM_ABI_VERSION = 15  # include/gpumatch.h
 GM_E_OVERFLOW = -4
 GM_E_STALE = -9
 GM_E_COMM = -7
@@ -83,7 +83,16 @@ EXPORTS = ["gm_create", "gm_destroy", "gm_abi_version", "gm_load_generation", "g
            "gm_stats", "gm_last_error", "gm_normalize_uris", "gm_counters_global", "gm_parse_requests",
            "gm_peers_init", "gm_select_peers", "gm_release_peers", "gm_peer_address", "gm_upstream_uris",
            "gm_update_upstream", "gm_peers_migrate", "gm_rejects", "gm_build_hash", "gm_sync_batches",
-           "gm_inflate_bodies", "gm_multipart_bodies", "gm_xml_bodies", "gm_auth_jwt", "gm_auth_info"]
+           "gm_inflate_bodies", "gm_multipart_bodies", "gm_xml_bodies", "gm_auth_jwt", "gm_auth_info",
+           "gm_ws_messages"]
+
+# gm_ws_messages (include/gpumatch.h): gm_ws_seg, gm_ws_result; status = GM_WS_* | reason << 8
+WS_SEG_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("pad", "<u4")])
+WS_RESULT_DTYPE = np.dtype([("status", "<u4"), ("consumed", "<u4"), ("stop", "<u4"), ("n_messages", "<u4")])
+GmWsSeg, GmWsResult = WS_SEG_DTYPE, WS_RESULT_DTYPE
+GM_WS_OK, GM_WS_CLOSED, GM_WS_DEFLATE, GM_WS_PROTO = 0, 1, 2, 3
+WS_REASON = {0: "", 1: "RSV", 2: "OPCODE", 3: "UNMASKED", 4: "CTRL_FRAG", 5: "CTRL_LEN", 6: "LENGTH", 7: "CONT",
+             8: "NESTED"}
 
 # gm_auth_jwt: out_auth[i] = code | reason << 8 (include/gpumatch.h)
 GM_AUTH_NONE, GM_AUTH_OK, GM_AUTH_DENY, GM_AUTH_DEFER = 0, 1, 2, 3
@@ -150,6 +159,9 @@ def lib():
         L.gm_auth_jwt.argtypes = [ctypes.c_void_p, ctypes.POINTER(GmBatch), ctypes.c_void_p, ctypes.c_uint64,
                                   ctypes.c_void_p, ctypes.c_void_p]
         L.gm_auth_info.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.gm_ws_messages.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]
         L.gm_rejects.argtypes =[ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         L.gm_build_hash.restype = ctypes.c_char_p
         L.gm_build_hash.argtypes = []
@@ -383,6 +395,41 @@ class Engine:
         out, off = d_out.cpu().numpy(), d_off.cpu().numpy()
         ln = d_len.cpu().numpy().view(np.uint32)
         return [None if ln[i] == GM_NONE else out[off[i]:off[i] + ln[i]].tobytes() for i in range(n)]
+
+    def ws_messages(self, wire_ptr, segs_ptr, n, out_ptr, out_cap, off_ptr, len_ptr, res_ptr, stream=0):
+        """gm_ws_messages on device pointers: the unmasked message view of every segment (async)."""
+        self._chk(lib().gm_ws_messages(self.h, wire_ptr, segs_ptr, n, out_ptr, out_cap, off_ptr, len_ptr, res_ptr,
+                                       stream))
+
+    def ws_messages_host(self, wire_bytes, segs, out_cap: int | None = None):
+        """Host bytes and (off, len) pairs in (staged through device tensors), (views, results) out:
+        the view bytes of every segment and a WS_RESULT_DTYPE array (the grammar of
+        include/gpumatch.h).  ``out_cap``: the view buffer's capacity, the sum of the lengths by default."""
+        import torch
+        n = len(segs)
+        dev = torch.device("cuda", self.device)
+        sg = np.zeros(max(n, 1), dtype=WS_SEG_DTYPE)
+        for i, (o, k) in enumerate(segs):
+            if o + k > len(wire_bytes):
+                raise ValueError(f"segment {i} lies outside the wire bytes")
+            sg[i] = (o, k, 0)
+        wire = np.zeros(len(wire_bytes) + 16, np.uint8)
+        wire[:len(wire_bytes)] = np.frombuffer(wire_bytes, np.uint8)
+        cap = int(sg["len"].sum()) if out_cap is None else out_cap
+        d_wire = torch.from_numpy(wire).to(dev)
+        d_segs = torch.from_numpy(sg.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_out = torch.zeros(cap + 16, dtype=torch.uint8, device=dev)
+        d_off = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        d_len = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        d_res = torch.zeros(4 * max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.ws_messages(d_wire.data_ptr(), d_segs.data_ptr(), n, d_out.data_ptr(), cap, d_off.data_ptr(),
+                         d_len.data_ptr(), d_res.data_ptr(), 0)
+        self.sync(0)
+        out, off = d_out.cpu().numpy(), d_off.cpu().numpy()
+        ln = d_len.cpu().numpy().view(np.uint32)
+        res = d_res.cpu().numpy().view(WS_RESULT_DTYPE)[:n]
+        return [out[off[i]:off[i] + ln[i]].tobytes() for i in range(n)], res
 
     def auth_jwt_ptr(self, reqs_ptr, arena_ptr, arena_len, n, verdicts_ptr, now, out_ptr, stream=0):
         """gm_auth_jwt on device pointers: the auth_jwt outcome of every verdict (async)."""
